@@ -20,12 +20,28 @@ never touches a GPU itself.  Under torchrun, WORLD_SIZE must equal --gpus.
 independent transforms is split by transform instead, rank r running B/G whole
 transforms (P = --workers, default 1) -- again no data-path collective.
 
-At G > 1 the optional final exchange (RCCL all-gather over xGMI + the
+At G > 1, with --full, the optional final exchange (RCCL all-gather over xGMI + the
 stride-P interleave into natural order) runs once after the timed region and
 is reported as config.allgather_ms (never part of value; --no-allgather skips
 it).  Every rank's own time and dominant-kernel roofline go to config.per_rank.
 
-Adds to the JSON line:
+A plain run (no --full) does only what the headline figure needs: it builds
+the plan with its input resident in HBM, runs --warmup untimed steps, times
+exactly --steps steps, writes the outputs when --dump-outputs is given and
+prints the line (value and ms_per_step; roofline, cpu_baseline and
+config.secondary are null).
+
+--dump-outputs DIR: after the timed steps, what the last timed step left in
+the output buffer a caller of pifft_execute_device receives, as DIR/out.npy
+(DIR/out_rank<r>.npy per rank at G > 1): an (elements, 2) array of (re, im)
+in the transform's own precision (float64 / float32).  An output above
+DUMP_MAX_BYTES (32 MiB over all ranks) is sampled at dump_sample_indices(), a
+fixed seeded choice of elements that depends on the output's length alone.
+The input is a function of --seed and the shape alone, so two builds run with
+the same arguments can be compared output for output.
+
+--full adds, after the timed region, everything else the benchmark measures
+or checks:
   roofline     : the dominant kernel's algorithmic bytes / its mean duration,
                  vs 8 TB/s.  The duration: after the timed region, a clean
                  loop of that kernel's launches alone, back to back on the
@@ -42,7 +58,7 @@ Adds to the JSON line:
                  reference source) at the SAME N, rank 0 of every job, at the
                  fastest p the box's CPU share supports (p = 16 under a
                  16-CPU quota), the reference's own p_to = 32 beside it
-  secondary    : (--gpus 1, default on) configs 1, 2 (whole and one GPU's
+  secondary    : (--gpus 1) configs 1, 2 (whole and one GPU's
                  slice) and 3 timed in the same run, each with its own
                  dominant-kernel roofline and a reference CPU baseline at the
                  same N
@@ -77,6 +93,10 @@ REF_P_TO = 32
 # planned below this, and below 0.8 x MemAvailable and any cgroup limit
 HOST_CMD_CAP = 256 << 30
 BENCH_PROC_RESERVE = 8 << 30  # this process (torch + HIP runtime) beside the reference
+# --dump-outputs: bytes written over all ranks; a larger output is sampled
+DUMP_MAX_BYTES = 32 << 20
+DUMP_SAMPLE_SEED = 0xD0FF
+DUMP_SAMPLE_EDGE = 1 << 12  # the sample leads with the output's first and last elements
 
 
 def _baseline_metric():
@@ -373,6 +393,38 @@ def spawn_ranks(gpus: int) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.run(cmd, env=env).returncode
+
+
+def dump_sample_indices(total: int, count: int):
+    """The `count` element indices --dump-outputs keeps of an output of
+    `total` elements too large to write whole: the first and the last
+    DUMP_SAMPLE_EDGE elements, the rest drawn uniformly (with a fixed seed)
+    from the whole range.  A function of (total, count) alone."""
+    import numpy as np
+    edge = min(DUMP_SAMPLE_EDGE, count // 4)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    mid = rng.integers(0, total, size=count - 2 * edge, dtype=np.int64)
+    return np.concatenate([np.arange(edge, dtype=np.int64), mid, np.arange(total - edge, total, dtype=np.int64)])
+
+
+def dump_outputs(torch, y, out_dir: str, rank: int, world: int) -> dict:
+    """--dump-outputs: this rank's output buffer `y` (complex, on the device)
+    as out_dir/out.npy (out_rank<r>.npy at world > 1), (elements, 2) = (re, im)
+    in y's own precision; whole when every rank's share of DUMP_MAX_BYTES holds
+    it, else the elements of dump_sample_indices (gathered on the device)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = y.numel()
+    keep = (DUMP_MAX_BYTES // world) // y.element_size()
+    flat = torch.view_as_real(y.reshape(-1))
+    if total > keep:
+        idx = torch.from_numpy(dump_sample_indices(total, keep)).to(y.device)
+        flat = flat.index_select(0, idx)
+    arr = np.ascontiguousarray(flat.cpu().numpy())
+    name = "out.npy" if world == 1 else f"out_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), arr)
+    return {"file": name, "elements": int(arr.shape[0]), "of": int(total), "sampled": bool(total > keep),
+            "dtype": str(arr.dtype)}
 
 
 class Job:
@@ -942,7 +994,7 @@ def compact_line(full: dict) -> dict:
     c = {k: cfg[k] for k in ("workload", "n", "workers", "workers_per_gpu", "batch", "batch_per_gpu", "shard",
                              "local_n", "passes", "parallelism", "hbm_GBps_per_step_algorithmic", "allgather_ms",
                              "allgather_error", "verify_error", "per_rank_error", "emulated_rank", "stage",
-                             "detail") if k in cfg}
+                             "full", "dumped", "detail") if k in cfg}
     if cfg.get("verify") is not None:
         c["verify"] = _pick(cfg["verify"], ("ok", "slices_bitwise", "slices_checked", "rel_l2", "bins_ok",
                                             "bins_max_err", "error", "note"))
@@ -1018,12 +1070,20 @@ def main() -> int:
     ap.add_argument("--allgather", dest="allgather", action="store_true", default=True,
                     help="at G > 1, time the optional RCCL all-gather + interleave after the timed region (default)")
     ap.add_argument("--no-allgather", dest="allgather", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline figure: "
+                         "per-launch times and the dominant-kernel roofline, the secondary configs, the reference "
+                         "CPU baselines and, at G > 1, the per-rank records, the all-gather and the split's "
+                         "self-check (default: the headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the output of the last timed step to DIR/out.npy (out_rank<r>.npy at G > 1) as "
+                         "(re, im) rows; a fixed seeded sample of an output above DUMP_MAX_BYTES")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip configs 1-3 (at 1 GPU) / 2-3 split over the GPUs and 5 (at 8 GPUs) beside the "
+                    help="(with --full) skip configs 1-3 (at 1 GPU) / 2-3 split over the GPUs and 5 (at 8 GPUs) beside the "
                          "headline step")
     ap.add_argument("--c5-log-n", type=int, default=32,
                     help="config 5 size at 8 GPUs (default 2^32; smaller only to rehearse the code path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the reference CPU baselines")
     ap.add_argument("--cpu-log-n", type=int, default=0, help="CPU baseline size (default: the headline N)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="reference pthreads for the CPU baseline (default: the reference's own p_to = 32, "
@@ -1109,14 +1169,19 @@ def main() -> int:
     local_s = job.run(args.steps, args.warmup, barrier)
     elapsed = pifft_dist.max_over_ranks(local_s, red_dev)
     ms_per_step = elapsed * 1e3 / args.steps
-    job.time_launches(max(5, args.steps // 2))  # after the timed region
-    rf = job.roofline(local_s * 1e3 / args.steps)
+    dumped = None
+    if args.dump_outputs:  # the last timed step's output, before anything else runs
+        dumped = dump_outputs(torch, job.y, args.dump_outputs, rank, world)
     desc = job.desc
     kernel_names = [job.plan.kernel_name(i) for i in range(desc["num_launches"])]
-    launches = job.launches(local_s * 1e3 / args.steps)
-    config_key = f"n2^{args.log_n}_f{args.prec}_b{b_count}_P{P}_q{count}"
-    rf["traffic"], rf["traffic_source"] = load_traffic(config_key, rf["launches"],
-                                                       [job.plan.kernel_name(i) for i in rf["launches"]])
+    rf = launches = None
+    if args.full:
+        job.time_launches(max(5, args.steps // 2))  # after the timed region
+        rf = job.roofline(local_s * 1e3 / args.steps)
+        launches = job.launches(local_s * 1e3 / args.steps)
+        config_key = f"n2^{args.log_n}_f{args.prec}_b{b_count}_P{P}_q{count}"
+        rf["traffic"], rf["traffic_source"] = load_traffic(config_key, rf["launches"],
+                                                           [job.plan.kernel_name(i) for i in rf["launches"]])
 
     total_bytes = sum(desc["launch_bytes"][: desc["num_launches"]])
     flops = 5.0 * n * args.log_n * args.batch  # the whole job's batch (every rank's share)
@@ -1158,13 +1223,15 @@ def main() -> int:
             "per_rank": None,
             "emulated_rank": args.as_rank or None,
             "secondary": None,
+            "full": args.full,
+            "dumped": dumped,
             "detail": os.path.relpath(args.detail, ROOT) if args.detail else None,
         },
         "roofline": rf,
         "cpu_baseline": None,
     }
     cfg = full["config"]
-    if dist is not None and rank == 0:
+    if dist is not None and rank == 0 and args.full:
         # the headline is complete here: print it before anything optional
         # runs (the first multi-GPU run executes the RCCL exchange for the
         # first time; CPU.c:485-492, worker 0 reports regardless of the
@@ -1173,7 +1240,7 @@ def main() -> int:
         emit(full, args.detail)
     cfg["stage"] = None
 
-    if dist is not None:
+    if dist is not None and args.full:
         mine = {"rank": rank, "gpu": gpu, "workers": [first, first + count], "batch": [b_first, b_first + b_count],
                 "ms_per_step": round(local_s * 1e3 / args.steps, 6), "dominant_ms": rf["mean_ms"],
                 "achieved": rf["achieved"], "frac": rf["frac"]}
@@ -1186,12 +1253,12 @@ def main() -> int:
 
     # the optional exchange and the split's self-check (exchange_and_verify:
     # every failure an *_error field, all ranks on the same branch)
-    if dist is not None and (args.shard == "batch" or count < P or world == 1):
+    if dist is not None and args.full and (args.shard == "batch" or count < P or world == 1):
         exchange_and_verify(pifft, torch, dist, job, rank, world, barrier, red_dev, cfg,
                             verify=args.shard == "workers" and (count < P or world == 1), gather=args.allgather)
     job.free()
 
-    if not args.no_secondary and not emulated:
+    if args.full and not args.no_secondary and not emulated:
         if dist is None and args.log_n == 28 and args.prec == 64 and args.batch == 1:
             cfg["secondary"] = secondary_configs(pifft, torch, gpu, args.steps, args.warmup, args.seed,
                                                  args.cpu_threads, not args.no_cpu_baseline)
@@ -1210,7 +1277,7 @@ def main() -> int:
     if rank == 0:
         # rank 0 of every job (also N > 1, so the driver's scaling lines carry
         # it), after the GPU work: the other ranks do not wait for it
-        if not emulated and not args.no_cpu_baseline:
+        if args.full and not emulated and not args.no_cpu_baseline:
             try:
                 full["cpu_baseline"] = headline_cpu_baseline(args.cpu_log_n or args.log_n, args.prec,
                                                              batch=args.batch, threads=args.cpu_threads or None)

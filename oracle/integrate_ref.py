@@ -62,8 +62,11 @@ def main() -> int:
             f.write(src)
         for suffix, extra in (("", []), ("-f64", ["-Dfloat=double"])):
             exe = os.path.join(out_dir, "fourier-parallel-pi-cpu-pthreads-gpu" + suffix)
+            # rpath relative to the binary: the tree may be built in one place
+            # and run from another
             subprocess.run(["gcc", "-O2", "-w", "-fopenmp", "-pthread", *extra, path, "-I", os.path.join(ROOT, "include"),
-                            "-L", lib, "-lpifft", "-Wl,-rpath," + lib, "-lm", "-o", exe], check=True)
+                            "-L", lib, "-lpifft", "-Wl,-rpath,$ORIGIN/../../cs87project-msolano2_amd", "-lm",
+                            "-o", exe], check=True)
     return 0
 
 

@@ -16,32 +16,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINE_MAX_CHARS = 7000  # bench.LINE_MAX_CHARS: the driver keeps the last ~8 KB of stdout
 
 
-def _bench(*args, env_extra=None, tmp=None):
-    """Runs bench.py; checks the printed line (one at N = 1; at N > 1 the
-    headline first, printed before the optional exchange, then the final
+def _bench(*args, env_extra=None, tmp=None, full=True):
+    """Runs bench.py --full (everything beside the headline steps: rooflines,
+    secondary configs, CPU baselines, the multi-GPU exchange and self-check;
+    full=False: a plain run); checks the printed line (one at N = 1; at N > 1
+    the headline first, printed before the optional exchange, then the final
     line) and returns the full record from its sidecar (--detail), with the
     printed line under "_line"."""
     import tempfile
     side = os.path.join(tmp or tempfile.mkdtemp(), "detail.json")
     env = dict(os.environ)
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--detail", side],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, *(["--full"] if full else []),
+                        "--detail", side],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     multi = ("--gpus" in args and args[args.index("--gpus") + 1] != "1") or "--pg" in args
-    assert len(lines) == (2 if multi else 1), r.stdout
+    assert len(lines) == (2 if multi and full else 1), r.stdout  # (a plain run prints its one line)
     for ln in lines:
         assert len(ln) <= LINE_MAX_CHARS, len(ln)
     line = json.loads(lines[-1])
-    if multi:
+    if multi and full:
         first = json.loads(lines[0])
         assert first["config"]["stage"].startswith("headline") and line["config"].get("stage") is None
         assert first["value"] == line["value"] and first["ms_per_step"] == line["ms_per_step"]
     with open(side) as f:
         d = json.load(f)
     assert d["value"] == line["value"] and d["ms_per_step"] == line["ms_per_step"]
-    assert line["roofline"].get("frac") == d["roofline"].get("frac")
+    assert (line["roofline"] is None) == (d["roofline"] is None) == (not full)
+    if full:
+        assert line["roofline"].get("frac") == d["roofline"].get("frac")
     for key, rec in (d["config"].get("secondary") or {}).items():  # every config's numbers are in the line
         lrec = line["config"]["secondary"][key]
         assert lrec.get("value") == rec.get("value") and lrec.get("ms_per_step") == rec.get("ms_per_step")
@@ -187,6 +192,50 @@ def test_bench_secondary_configs():
     assert sec["C4_f32"]["dtype"] == "f32" and sec["C4_f32"]["n"] == 1 << 28
     assert sec["C3"]["dtype"] == "f32" and sec["C3"]["batch"] == 4096
     assert sec["C2"]["workers"] == 8 and sec["C2_slice"]["workers_in_plan"] == 1
+
+
+@pytest.mark.parametrize("log_n,sampled", [(12, False), (22, True)])
+def test_bench_plain_run_dumps_its_outputs(log_n, sampled, tmp_path):
+    """A plain run (no --full) times the headline steps only -- no roofline,
+    CPU baseline or secondary config -- and --dump-outputs writes the last
+    timed step's result: whole at 2^12, the fixed sample of
+    bench.dump_sample_indices at 2^22 (64 MiB of fp64 > DUMP_MAX_BYTES).
+    Checked against the oracle's transform of the oracle's input (the bench
+    input is the same generator on the device): rel-L2 <= 1e-12, the fp64
+    tolerance of smoke() and of the bench's own self-check."""
+    import numpy as np
+    import pifft_oracle as oracle
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    d = _bench("--gpus", "1", "--log-n", str(log_n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out),
+               tmp=str(tmp_path), full=False)
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    n = 1 << log_n
+    assert abs(d["value"] - 5.0 * n * log_n / (d["ms_per_step"] * 1e-3) / 1e9) <= \
+        d["value"] * (1e-3 + 1e-6 / d["ms_per_step"]) + 0.01
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    cfg = d["config"]
+    assert cfg["full"] is False and cfg["secondary"] is None and cfg["launches"] is None
+    assert os.listdir(out) == ["out.npy"]
+    got = np.load(out / "out.npy")
+    assert got.dtype == np.float64 and got.ndim == 2 and got.shape[1] == 2
+    assert got.nbytes <= bench.DUMP_MAX_BYTES
+    want = oracle.fft(oracle.generate(n, np.complex128), P=1)
+    if sampled:
+        idx = bench.dump_sample_indices(n, bench.DUMP_MAX_BYTES // 16)
+        assert got.shape[0] == len(idx) < n
+        want = want[idx]
+    else:
+        assert got.shape[0] == n
+    assert cfg["dumped"] == {"file": "out.npy", "elements": got.shape[0], "of": n, "sampled": sampled,
+                             "dtype": "float64"}
+    got = got[:, 0] + 1j * got[:, 1]
+    err = float(np.linalg.norm(got - want) / np.linalg.norm(want))
+    assert err <= 1e-12, err
 
 
 def test_bench_exchange_failure_keeps_the_line():

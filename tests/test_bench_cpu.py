@@ -104,6 +104,21 @@ def test_headline_cpu_baseline_runs_the_reference():
     assert "p=2 pthreads" in rec["sample"]
 
 
+def test_dump_sample_indices_are_fixed_and_in_range():
+    """--dump-outputs' sample of a large output: a function of the output's
+    length and the count alone (two runs keep the same elements), inside the
+    output, leading with its first and ending with its last elements."""
+    import numpy as np
+    for total in (1 << 22, 1 << 28, 1 << 32):
+        count = bench.DUMP_MAX_BYTES // 16
+        a, b = bench.dump_sample_indices(total, count), bench.dump_sample_indices(total, count)
+        assert a.dtype == np.int64 and len(a) == count and np.array_equal(a, b)
+        assert a.min() == 0 and a.max() == total - 1
+        e = bench.DUMP_SAMPLE_EDGE
+        assert np.array_equal(a[:e], np.arange(e)) and np.array_equal(a[-e:], np.arange(total - e, total))
+    assert len(bench.dump_sample_indices(1 << 20, 8)) == 8  # (a many-rank job's small share)
+
+
 def test_pg_is_a_process_group_option():
     """--pg opens a process group at one rank (bench.py's multi-GPU branch on
     one GPU); it cannot be combined with --as-rank, the single-process

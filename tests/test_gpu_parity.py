@@ -678,15 +678,21 @@ def test_reference_run_with_pifft_backend(prec):
     fan-out of run() replaced by pifft_plan_create + pifft_execute."""
     import subprocess
     exe = _ref_gpu(prec)
+    # the binary is built in one tree and may run from another (or through a
+    # linked oracle/_ref, where a run path relative to the binary points
+    # nowhere): it gets the very libpifft.so this suite loads, by directory
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(
+        [os.path.dirname(os.path.abspath(pifft.LIB_PATH))] + [p for p in [env.get("LD_LIBRARY_PATH")] if p])
     for P in ("1", "2", "4", "8"):
-        r = subprocess.run([exe, "-t", "-p", P], capture_output=True, text=True, timeout=120)
+        r = subprocess.run([exe, "-t", "-p", P], capture_output=True, text=True, timeout=120, env=env)
         assert r.returncode == 0, r.stderr
         assert "Output is correct. Test passed." in r.stdout
-    r = subprocess.run([exe, "-n", "1048576", "-p", "8", "-o"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, "-n", "1048576", "-p", "8", "-o"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stderr
     cols = r.stdout.strip().split("\t")
     assert len(cols) == 5 and cols[:2] == ["1048576", "8"]
-    r = subprocess.run([exe, "-n", "1048576"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, "-n", "1048576"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 1 and "Missing option: -p" in r.stderr
 
 

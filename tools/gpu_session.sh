@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/gpu_session.sh <tag> <stages> [tests...] -- one GPU evidence session (rounds 5-6).
-# stages: any of t (GPU tests + smoke), b (bench.py as the driver runs it; the
-#   printed line, and its sidecar with the per-launch detail),
+# stages: any of t (GPU tests + smoke), b (bench.py --full: every config, rooflines
+#   and CPU baselines; the printed line, and its sidecar with the per-launch detail),
 #   s (rocprofv3 --kernel-trace --stats of bench.py in the same session, then
 #      tools/check_rooflines.py on both lines),
 #   p (PMC traffic, tools/pmc_traffic.py, FETCH_SIZE / WRITE_SIZE passes, of
@@ -28,13 +28,13 @@ if [[ "$stages" == *t* ]]; then
   tail -1 "$out/smoke.txt"
 fi
 if [[ "$stages" == *b* ]]; then
-  timeout -k 10 900 python -u bench.py --detail "$out/${tag}_bench_detail.json" > "$out/bench.log" 2>&1 || { tail -20 "$out/bench.log"; exit 1; }
+  timeout -k 10 900 python -u bench.py --full --detail "$out/${tag}_bench_detail.json" > "$out/bench.log" 2>&1 || { tail -20 "$out/bench.log"; exit 1; }
   grep '^{' "$out/bench.log" | tail -1 > "$out/${tag}_bench.json" || exit 1
   python3 -c "import json; s=open('$out/${tag}_bench.json').read(); d=json.loads(s); print('chars', len(s), 'value', d['value'], 'ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'traffic', d['roofline']['traffic']); [print(k, v.get('ms_per_step'), (v.get('roofline') or {}).get('frac'), (v.get('roofline') or {}).get('traffic'), (v.get('cpu_baseline') or {}).get('value')) for k, v in d['config']['secondary'].items()]; print('cpu', d['cpu_baseline']['value'], d['cpu_baseline']['cores'])"
 fi
 if [[ "$stages" == *s* ]]; then
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$out/stats_sec" -o sec -- \
-      python3 -u bench.py --no-cpu-baseline --steps 20 --warmup 5 --detail "$out/stats_detail.json" > "$out/stats_sec.log" 2>&1 || { tail -20 "$out/stats_sec.log"; exit 1; }
+      python3 -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --detail "$out/stats_detail.json" > "$out/stats_sec.log" 2>&1 || { tail -20 "$out/stats_sec.log"; exit 1; }
   rocpd2summary -i "$out/stats_sec/sec_results.db" -f csv -d "$out/sum_sec" -o sec > /dev/null 2>&1 || exit 1
   grep '^{' "$out/stats_sec.log" | tail -1 > "$out/${tag}_bench_under_rocprof.json" || true
   if [ -f "$out/${tag}_bench.json" ]; then
