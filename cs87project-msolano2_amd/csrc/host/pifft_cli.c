@@ -11,7 +11,7 @@
  *            show_usage, print_input/print_output, verify_results (CPU.c:293-302, 659-705)
  *
  *   pifft { -n <n> -p <p> [-o] | -t } [-f 32|64] [-b batch] [-s seed] [-g gpus]
- *         [-w file] [-r] [-u] [-x] [-W warmups] [-l]
+ *         [-w file] [-r] [-u] [-x] [-i] [-W warmups] [-l]
  *
  * Output: the reference's 5-column TSV "n p total stage1 stage2" in ms
  * (CPU.c:485-492), once.  stage 1 = tree, stage 2 = local FFT (+ reorder),
@@ -28,7 +28,8 @@
  * pass: stage 1 = the tree alone, as the reference's funnel timer, for the
  * cost-law fit of analyze-results.R:56), -x extra columns (GFLOP/s, GB/s over
  * the wall total, then the kernel-only stage sums: stage times without the
- * gaps between launches),
+ * gaps between launches), -i the unnormalised inverse transform
+ * (PIFFT_INVERSE: same launches and TSV columns; valid with -g -r -u -x -w -b -f),
  * -W untimed warm-up runs before the timed one (default 1; code-object load),
  * -l list GPUs (the how-many-* utilities), -R rehearse a -g split with every
  * plan on GPU 0 (a one-GPU box runs the multi-plan path).  -n is parsed as
@@ -71,12 +72,13 @@ typedef struct tr {
     int bitrev;          /* -r */
     int separate_tree;   /* -u */
     int rehearse;        /* -R */
+    int inverse;         /* -i */
 } tr_t;
 
 static void show_usage(void) {
     print_out("\nusage:\n"
               "  pifft { -n <n> -p <p> [-o] | -t } [-f 32|64] [-b <batch>] [-s <seed>]\n"
-              "        [-g <gpus>] [-w <file>] [-r] [-u] [-x] [-W <warmups>] [-l] [-R]\n"
+              "        [-g <gpus>] [-w <file>] [-r] [-u] [-x] [-i] [-W <warmups>] [-l] [-R]\n"
               "\noptions:\n"
               "  -n <n>     power of two input size\n"
               "  -p <p>     power of two number of processors (less than n)\n"
@@ -90,6 +92,7 @@ static void show_usage(void) {
               "  -r         output in the reference's bit-reversed scratch order\n"
               "  -u         tree stage as its own launch (stage 1 = the tree alone)\n"
               "  -x         extra columns: GFLOP/s, algorithmic GB/s, kernel-only stage 1 / 2 ms\n"
+              "  -i         inverse transform (unnormalised, e^{+2 pi i nk/n}; scale by 1/n yourself)\n"
               "  -W <w>     untimed warm-up runs (default 1)\n"
               "  -l         list GPUs and exit\n"
               "  -R         rehearse the -g split with every plan on GPU 0\n"
@@ -128,7 +131,7 @@ int setup_from_args(tr_t* t, int argc, char** argv) {
     t->batch = 1;
     t->gpus = 1;
     t->warmups = 1;
-    while ((ret = getopt(argc, argv, "n:p:tof:b:s:g:w:ruxW:lR")) != -1) {
+    while ((ret = getopt(argc, argv, "n:p:tof:b:s:g:w:ruxiW:lR")) != -1) {
         switch (ret) {
             case 'n':
                 if (parse_u64(optarg, &num) || !(num > 1) || !is_power_of_two_u64(num)) {
@@ -195,6 +198,9 @@ int setup_from_args(tr_t* t, int argc, char** argv) {
                 break;
             case 'x':
                 t->extra = 1;
+                break;
+            case 'i':
+                t->inverse = 1;
                 break;
             case 'R':
                 t->rehearse = 1;
@@ -346,10 +352,11 @@ static int check_split(const tr_t* t, pifft_plan* const* plans) {
     void* rep = malloc(total * esz(t));
     pifft_plan* one = NULL;
     int rc = -1;
+    const int dir = t->inverse ? PIFFT_INVERSE : 0;
     if (!ref || !rep) goto out;
     /* the whole transform on GPU 0, all P workers (same order as the split) */
     if (pifft_plan_create_slices(&one, t->N, t->P, 0, t->P, t->batch, t->prec, 0,
-                                 t->bitrev ? PIFFT_OUT_BITREV : PIFFT_OUT_NATURAL) ||
+                                 (t->bitrev ? PIFFT_OUT_BITREV : PIFFT_OUT_NATURAL) | dir) ||
         pifft_execute(one, t->in, ref, NULL, NULL)) {
         stderr_out("%s\n", pifft_last_error());
         goto out;
@@ -370,7 +377,7 @@ static int check_split(const tr_t* t, pifft_plan* const* plans) {
         memset(rep, 0xff, total * esz(t));  /* NaN pattern: positions the plan does not write */
         pifft_plan* p = NULL;
         if (pifft_plan_create_slices(&p, t->N, t->P, g * per, per, t->batch, t->prec, 0,
-                                     t->bitrev ? PIFFT_OUT_BITREV : PIFFT_OUT_SLICES) ||
+                                     (t->bitrev ? PIFFT_OUT_BITREV : PIFFT_OUT_SLICES) | dir) ||
             pifft_execute(p, t->in, rep, NULL, NULL)) {
             stderr_out("%s\n", pifft_last_error());
             if (p) pifft_plan_destroy(p);
@@ -411,7 +418,7 @@ int run(tr_t* t) {
     int rc = -1, split = 0;
     double s1 = 0, s2 = 0;
     if (initialize_data(t)) goto done;
-    const int sep = t->separate_tree ? PIFFT_SEPARATE_TREE : 0;
+    const int sep = (t->separate_tree ? PIFFT_SEPARATE_TREE : 0) | (t->inverse ? PIFFT_INVERSE : 0);
     for (uint32_t g = 0; g < G; g++) {
         int r = (G == 1) ? pifft_plan_create_slices(&plans[g], t->N, t->P, 0, t->P, t->batch, t->prec, 0,
                                                     (t->bitrev ? PIFFT_OUT_BITREV : PIFFT_OUT_NATURAL) | sep)

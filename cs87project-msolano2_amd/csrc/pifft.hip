@@ -132,6 +132,15 @@ PIFFT_DECL_PART(4)
 PIFFT_DECL_PART(5)
 PIFFT_DECL_PART(6)
 PIFFT_DECL_PART(7)
+#define PIFFT_DECL_TWINS(k) extern "C" const TwinKernel* pifft_twin_table_##k(int* n);
+PIFFT_DECL_TWINS(0)
+PIFFT_DECL_TWINS(1)
+PIFFT_DECL_TWINS(2)
+PIFFT_DECL_TWINS(3)
+PIFFT_DECL_TWINS(4)
+PIFFT_DECL_TWINS(5)
+PIFFT_DECL_TWINS(6)
+PIFFT_DECL_TWINS(7)
 namespace {
 static_assert(PIFFT_NPART == 8, "update the part list");
 
@@ -171,6 +180,61 @@ const PassKernel* find_pass(int prec, int R, int C, int mode, int nts = 0, int l
     return nullptr;
 }
 
+// The swapping twins of the instances (inverse plans), a table of their own:
+// the registry above, pifft_instance_* and the committed instance lists know
+// the forward instances only.
+const std::vector<TwinKernel>& twin_kernels() {
+    static const std::vector<TwinKernel> all = [] {
+        std::vector<TwinKernel> v;
+        const TwinKernel* (*parts[])(int*) = {pifft_twin_table_0, pifft_twin_table_1, pifft_twin_table_2,
+                                               pifft_twin_table_3, pifft_twin_table_4, pifft_twin_table_5,
+                                               pifft_twin_table_6, pifft_twin_table_7};
+        for (auto f : parts) {
+            int n = 0;
+            const TwinKernel* t = f(&n);
+            for (int i = 0; i < n; i++)
+                if (t[i].fn) v.push_back(t[i]);  // (empty slots: twins no inverse plan reaches)
+        }
+        return v;
+    }();
+    return all;
+}
+
+// the twin of forward instance k with swaps sw (1 in, 2 out, 3 both), or null
+const TwinKernel* find_twin(const PassKernel& k, int sw) {
+    for (const TwinKernel& t : twin_kernels())
+        if (t.sw == sw && t.prec == k.prec && t.R == k.R && t.C == k.C && t.mode == k.mode && t.nts == k.nts &&
+            t.lp == k.lp && t.vpt == k.vpt)
+            return &t;
+    return nullptr;
+}
+
+// the twins of the tree and interleave kernels: (forward kernel, sw) -> twin
+const void* find_aux_twin(const void* fn, int sw) {
+    struct Aux {
+        const void* fwd;
+        int sw;
+        const void* twin;
+    };
+#define PIFFT_TREE_TWINS(T, L)                                                                    \
+    {(const void*)&k_tree<T, L>, 1, (const void*)&k_tree_sw<T, L, 1>},                            \
+        {(const void*)&k_tree<T, L>, 2, (const void*)&k_tree_sw<T, L, 2>},                        \
+        {(const void*)&k_tree<T, L>, 3, (const void*)&k_tree_sw<T, L, 3>},                        \
+        {(const void*)&k_tree_wil<T, L>, 1, (const void*)&k_tree_wil_sw<T, L, 1>}
+    static const Aux aux[] = {
+        PIFFT_TREE_TWINS(double, 1), PIFFT_TREE_TWINS(double, 2), PIFFT_TREE_TWINS(double, 3), PIFFT_TREE_TWINS(double, 4),
+        PIFFT_TREE_TWINS(float, 1),  PIFFT_TREE_TWINS(float, 2),  PIFFT_TREE_TWINS(float, 3),  PIFFT_TREE_TWINS(float, 4),
+        {(const void*)&k_interleave<double>, 2, (const void*)&k_interleave_sw<double, 2>},
+        {(const void*)&k_interleave<float>, 2, (const void*)&k_interleave_sw<float, 2>},
+        {(const void*)&k_interleave_tile<double>, 2, (const void*)&k_interleave_tile_sw<double, 2>},
+        {(const void*)&k_interleave_tile<float>, 2, (const void*)&k_interleave_tile_sw<float, 2>},
+    };
+#undef PIFFT_TREE_TWINS
+    for (const Aux& a : aux)
+        if (a.fwd == fn && a.sw == sw) return a.twin;
+    return nullptr;
+}
+
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
@@ -206,6 +270,7 @@ struct pifft_plan {
     bool ilv = false;     // the last pass stores natural order itself (PassArgs::ilv_log)
     bool wil = false;     // worker-interleaved layout (PassArgs::wil, MODE | 8 passes)
     bool separate_tree = false;  // PIFFT_SEPARATE_TREE: never fuse the tree into a pass
+    bool inverse = false;        // PIFFT_INVERSE: the first / last launch swap re/im (make_inverse)
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -1170,6 +1235,42 @@ int build_plan(pifft_plan* p, bool dry = false) {
     return 0;
 }
 
+// PIFFT_INVERSE: IDFT(x) = swap(DFT(swap(x))), swap(a + bi) = b + ai, for the
+// whole linear transform (tree, local FFT, any output order).  The plan is the
+// forward plan build_plan made; the one launch that reads the caller's input
+// becomes its twin swapping what it loads, the one launch that writes the
+// caller's output its twin swapping what it stores (one launch: both).  No
+// launch, byte or table more; the result equals swap(forward(swap(x))) bit
+// for bit.  Step::pk keeps the forward instance the twin derives from.
+int make_inverse(pifft_plan* p, bool dry) {
+    if (p->steps.empty()) return fail("empty plan");
+    const size_t last = p->steps.size() - 1;
+    if (p->steps[0].src != BUF_IN || p->steps[last].dst != BUF_OUT) return fail("inverse plan: unexpected buffer chain");
+    for (size_t i = 1; i <= last; i++)
+        if (p->steps[i].src == BUF_IN) return fail("inverse plan: launch %zu reads the input again", i);
+    for (size_t i = 0; i <= last; i++) {
+        const int sw = (i == 0 ? 1 : 0) | (i == last ? 2 : 0);
+        if (!sw) continue;
+        Step& s = p->steps[i];
+        if (s.kind == STEP_PASS || s.kind == STEP_TREE_PASS) {
+            const PassKernel& k = *s.pk;
+            const TwinKernel* t = find_twin(k, sw);
+            if (!t)
+                return fail("no inverse twin (swap %d) of pass kernel prec=%d R=%d C=%d mode=%d nts=%d lp=%d vpt=%d", sw,
+                            k.prec, k.R, k.C, k.mode, k.nts, k.lp, k.vpt);
+            s.fn = t->fn;
+        } else {
+            const void* t = find_aux_twin(s.fn, sw);
+            if (!t) return fail("no inverse twin (swap %d) of the %s kernel of launch %zu", sw,
+                                s.kind == STEP_TREE ? "tree" : "interleave", i);
+            s.fn = t;
+        }
+        if (s.lds > 65536 && !dry)
+            (void)hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
+    }
+    return 0;
+}
+
 int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint32_t count,
            uint32_t batch, int prec, int device, int flags, bool dry = false) {
     if (!out) return fail("plan pointer is NULL");
@@ -1181,11 +1282,15 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
         return fail("invalid worker range [%u, %u) of %u", first, first + count, workers);
     if (batch == 0) return fail("batch must be >= 1");
     if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
-    const int order = flags & ~PIFFT_SEPARATE_TREE;
+    const int order = flags & ~(PIFFT_SEPARATE_TREE | PIFFT_INVERSE);
     if (order != PIFFT_OUT_NATURAL && order != PIFFT_OUT_SLICES && order != PIFFT_OUT_BITREV)
         return fail("unknown flags %d", flags);
+    // (flags name an order for a worker range: the value is as unknown for a
+    // partial range -- PIFFT_INVERSE alone, say, which implies natural order --
+    // as an undefined bit is, and the message says which rule it broke)
     if (order == PIFFT_OUT_NATURAL && count != workers)
-        return fail("natural-order output needs all workers on one plan (use PIFFT_OUT_SLICES)");
+        return fail("unknown flags %d for workers [%u, %u) of %u: natural-order output needs all workers on one plan "
+                    "(use PIFFT_OUT_SLICES)", flags, first, first + count, workers);
     if (!dry) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available");
@@ -1203,6 +1308,7 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
     p->natural = (order == PIFFT_OUT_NATURAL);
     p->bitrev = (order == PIFFT_OUT_BITREV);
     p->separate_tree = (flags & PIFFT_SEPARATE_TREE) != 0;
+    p->inverse = (flags & PIFFT_INVERSE) != 0;
     p->esz = prec == PIFFT_F64 ? 16 : 8;
     p->lp = ilog2u(workers);
     p->log_n = ilog2u(n);
@@ -1210,7 +1316,7 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
     p->m = n >> p->lp;
     if (dry) p->device = -1;
     DeviceGuard g(dry ? -1 : device);
-    if (build_plan(p, dry)) {
+    if (build_plan(p, dry) || (p->inverse && make_inverse(p, dry))) {
         std::string keep = g_err;
         release(p);
         g_err = keep;
@@ -1408,6 +1514,8 @@ int check_cover(pifft_plan* const* plans, int np, bool quiet) {
         if (!p) return quiet ? -1 : fail("plan %d is NULL", i);
         if (p->n != plans[0]->n || p->P != plans[0]->P || p->batch != plans[0]->batch || p->prec != plans[0]->prec)
             return quiet ? -1 : fail("plans of a gather must share n, workers, batch and precision");
+        if (p->inverse != plans[0]->inverse)
+            return quiet ? -1 : fail("plans of a gather must share the direction (PIFFT_INVERSE on all or none)");
         if (p->natural || p->bitrev)
             return quiet ? -1 : fail("plan %d: a gather needs slice-major plans (PIFFT_OUT_SLICES)", i);
         order.push_back(i);
@@ -1915,6 +2023,8 @@ int pifft_execute_group(pifft_plan** plans, int np, const void* host_in, void* h
         if (plans[i]->n != plans[0]->n || plans[i]->batch != plans[0]->batch ||
             plans[i]->prec != plans[0]->prec)
             return fail("plans of a group must share n, batch and precision");
+        if (plans[i]->inverse != plans[0]->inverse)
+            return fail("plans of a group must share the direction (PIFFT_INVERSE on all or none)");
     }
     // stage the input on every device (outside the timed region, like the
     // reference's per-worker memcpy of the whole input, CPU.c:407): one copy
@@ -2095,6 +2205,7 @@ int pifft_allgather(pifft_plan* const* plans, int nplans, const void* const* d_s
 
 int pifft_tree_device(pifft_plan* p, const void* d_in, void* d_seg, void* stream) {
     if (check_buffers(p, d_in, d_seg)) return -1;
+    if (p->inverse) return fail("pifft_tree_device: forward plans only (the reference's tree)");
     DeviceGuard g(p->device);
     hipStream_t st = (hipStream_t)stream;  // NULL = the default stream
     if (p->tree_only.empty()) {  // P == 1: the segment is the input

@@ -176,9 +176,34 @@ template <typename T>
 constexpr bool vec_nt() {
     return PIFFT_VEC_NT == 1 || (PIFFT_VEC_NT == 2 && sizeof(T) == 4);
 }
-template <bool NTS, typename T>
+// Inverse transforms (PIFFT_INVERSE): IDFT(x) = swap(DFT(swap(x))) with
+// swap(a + bi) = b + ai, so an inverse plan is the forward plan whose one
+// launch reading the caller's input swaps re/im of every value it loads
+// (SW bit 0) and whose one launch writing the caller's output swaps every
+// value it stores (SW bit 1).  SW is a compile-time selector of the swapping
+// twins (k_pass_sw, k_tree_sw, ...); the swaps are register renames -- no
+// arithmetic, no select -- and the forward kernels are the SW = 0 bodies.
+// ld_stream / st_stream take SW themselves, and the few direct sites branch
+// with `if constexpr`: at SW = 0 every statement is the forward code as it was
+// (routed through a by-value helper even at SW = 0, a third of the forward
+// instances compiled to differently scheduled code; this way their code
+// objects are byte for byte what they were before the twins existed).
+template <int SW, typename T>
+__device__ __forceinline__ cx<T> sw_in(cx<T> v) {
+    if constexpr (SW & 1) return cx<T>{v.im, v.re};
+    else return v;
+}
+template <int SW, typename T>
+__device__ __forceinline__ cx<T> sw_out(cx<T> v) {
+    if constexpr (SW & 2) return cx<T>{v.im, v.re};
+    else return v;
+}
+template <bool NTS, int SW = 0, typename T>
 __device__ __forceinline__ cx<T> ld_stream(const cx<T>* p) {
-    if constexpr (NTS && PIFFT_NT_LOADS && vec_nt<T>()) {
+    if constexpr (SW & 1) {
+        const cx<T> r = ld_stream<NTS>(p);
+        return cx<T>{r.im, r.re};
+    } else if constexpr (NTS && PIFFT_NT_LOADS && vec_nt<T>()) {
         const vec2_t<T> r = __builtin_nontemporal_load(reinterpret_cast<const vec2_t<T>*>(p));
         return cx<T>{r.x, r.y};
     } else if constexpr (NTS && PIFFT_NT_LOADS) {
@@ -190,9 +215,11 @@ __device__ __forceinline__ cx<T> ld_stream(const cx<T>* p) {
         return *p;
     }
 }
-template <bool NTS, typename T>
+template <bool NTS, int SW = 0, typename T>
 __device__ __forceinline__ void st_stream(cx<T>* p, cx<T> v) {
-    if constexpr (NTS && PIFFT_NT_STORES && vec_nt<T>()) {
+    if constexpr (SW & 2) {
+        st_stream<NTS>(p, cx<T>{v.im, v.re});
+    } else if constexpr (NTS && PIFFT_NT_STORES && vec_nt<T>()) {
         vec2_t<T> r;
         r.x = v.re;
         r.y = v.im;
@@ -840,7 +867,7 @@ constexpr bool pass_tw_prefetch() {
 // transpose per component hands them to the pass's first stage (lanes across
 // lines, as MODE 10).  Replaces the all-worker tree launch (k_tree_wil),
 // which wrote the N tree values and had the first pass read them back.
-template <typename T, int R, int C, int LP, int VPT, int NTS>
+template <typename T, int R, int C, int LP, int VPT, int NTS, int SW = 0>
 __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>* v, int tid, uint64_t tile) {
     using C2 = cx<T>;
     using Sh = PassShape<R, VPT>;
@@ -866,7 +893,7 @@ __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>
         const uint64_t i = j0 + (uint64_t)(p % J) + ((uint64_t)(p / J) << log_lb);
         C2 w[P];
 #pragma unroll
-        for (int m = 0; m < P; m++) w[m] = ld_stream<nt_loads(NTS)>(x + i + ((uint64_t)m << log_m));
+        for (int m = 0; m < P; m++) w[m] = ld_stream<nt_loads(NTS), SW>(x + i + ((uint64_t)m << log_m));
         tree_levels<T, LP>(w, a.tree, i, log_m, 0, 0, 0, (uint64_t)(h * H), (uint64_t)(h * H + H));
         const int jl = p % J, r = p / J;
 #pragma unroll
@@ -902,7 +929,7 @@ __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>
         const int p = tid + u * NT;  // position: J adjacent j (lanes), then r
         const uint64_t i = j0 + (uint64_t)(p % J) + ((uint64_t)(p / J) << log_lb);
 #pragma unroll
-        for (int m = 0; m < P; m++) w[u][m] = ld_stream<nt_loads(NTS)>(x + i + ((uint64_t)m << log_m));
+        for (int m = 0; m < P; m++) w[u][m] = ld_stream<nt_loads(NTS), SW>(x + i + ((uint64_t)m << log_m));
     }
     // every level's twiddles in one round trip beside the leaves (where the
     // instance has the registers: <= 2 waves per SIMD, i.e. the latency-bound
@@ -951,7 +978,7 @@ __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>
 #ifndef PIFFT_SERIAL_BFLY
 #define PIFFT_SERIAL_BFLY 1
 #endif
-template <typename T, int R, int C, int MODE, int NTS, int LP, int S, int VPT>
+template <typename T, int R, int C, int MODE, int NTS, int LP, int S, int VPT, int SW = 0>
 __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v, cx<T>* pre, int tid, uint64_t tile,
                                             cx<T>* twp) {
     using C2 = cx<T>;
@@ -1014,7 +1041,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
     }
     if constexpr (St::first && BM == 3 && WIL) {
         // ---- MODE 11: every worker's tree, then the first stage's inputs via LDS ----
-        wil_tree_to_lds<T, R, C, LP, VPT, NTS>(a, lds, v, tid, tile);
+        wil_tree_to_lds<T, R, C, LP, VPT, NTS, SW>(a, lds, v, tid, tile);
     } else if constexpr (St::first) {
         // ---- inputs straight from HBM (all loads issued before any use) ----
         const C2* __restrict__ in = static_cast<const C2*>(a.in);
@@ -1068,7 +1095,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                         const C2* leaf = lsrc + ((uint64_t)((k0 + g) * NB) << log_lb);
 #pragma unroll
                         for (int m = 0; m < P; m++)
-                            w[g][m] = ok ? ld_stream<nt_loads(NTS)>(leaf + ((uint64_t)m << log_m)) : C2{(T)0, (T)0};
+                            w[g][m] = ok ? ld_stream<nt_loads(NTS), SW>(leaf + ((uint64_t)m << log_m)) : C2{(T)0, (T)0};
                     }
                     static_for<0, G, 1>([&](auto gc) {
                         constexpr int g = decltype(gc)::value;
@@ -1083,11 +1110,11 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                 const C2* row = in + bin * a.in_bstride + j + (uint64_t)b * rs;
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS)>(row + (uint64_t)(k * NB) * rs) : C2{(T)0, (T)0};
+                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS), SW>(row + (uint64_t)(k * NB) * rs) : C2{(T)0, (T)0};
             } else {
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS)>(src + ((uint64_t)(k * NB) << les)) : C2{(T)0, (T)0};
+                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << les)) : C2{(T)0, (T)0};
             }
         }
     }
@@ -1190,7 +1217,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                     C2* dst = out + bt * a.out_bstride + (pos << wil) + slot;
                     const uint32_t ks = lns + wil;
 #pragma unroll
-                    for (int k = 0; k < q; k++) st_stream<nt_stores(NTS)>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
+                    for (int k = 0; k < q; k++) st_stream<nt_stores(NTS), SW>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
                 } else if constexpr (!BREV) {
                     // (ilv_log = 0: dst = out + bt out_bstride + pos + k NB 2^lns)
                     const uint32_t il = a.ilv_log;
@@ -1200,7 +1227,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                     C2* dst = out + (bt >> il) * a.out_bstride + rq + (pos << il) + pad;
                     const uint32_t ks = lns + il;
 #pragma unroll
-                    for (int k = 0; k < q; k++) st_stream<nt_stores(NTS)>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
+                    for (int k = 0; k < q; k++) st_stream<nt_stores(NTS), SW>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
                     if constexpr (serial && PIFFT_SERIAL_BFLY >= 2) __builtin_amdgcn_sched_barrier(0);
                 } else {
                     C2* dst = out + bt * a.out_bstride;
@@ -1208,7 +1235,8 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
 #pragma unroll
                     for (int k = 0; k < q; k++) {
                         const uint64_t pk = pos + ((uint64_t)(k * NB) << lns);
-                        dst[sh < 64 ? __builtin_bitreverse64(pk) >> sh : 0] = v[u * q + k];
+                        if constexpr (SW & 2) dst[sh < 64 ? __builtin_bitreverse64(pk) >> sh : 0] = sw_out<SW>(v[u * q + k]);
+                        else dst[sh < 64 ? __builtin_bitreverse64(pk) >> sh : 0] = v[u * q + k];
                     }
                 }
             }
@@ -1230,12 +1258,12 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
 #pragma unroll
             for (int g = 0; g < 8; g++) pl_swap<16>(v[2 * g], v[2 * g + 1]);
         }
-        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT>(a, lds, v, pre, tid, tile, twp);
+        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT, SW>(a, lds, v, pre, tid, tile, twp);
     } else if constexpr (PIFFT_DIAG_NO_XCHG && MODE != 11) {
         // diagnostics build only (timing, WRONG results): no hand-off at all --
         // the upper bound of what any register exchange (DPP, ds_swizzle,
         // permlane) could save on this pass (round 6, profiles/sessions/gpu_r06w.sh)
-        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT>(a, lds, v, pre, tid, tile, twp);
+        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT, SW>(a, lds, v, pre, tid, tile, twp);
     } else {
         // ---- exchange with stage S+1 through LDS, one component at a time ----
         using Nx = Stage<R, C, SM, S + 1, VPT>;
@@ -1266,7 +1294,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                 }
             }
         }
-        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT>(a, lds, v, pre, tid, tile, twp);
+        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT, SW>(a, lds, v, pre, tid, tile, twp);
     }
 }
 
@@ -1327,7 +1355,7 @@ __device__ __forceinline__ cx<f2> pk_pair(cx<float> a, cx<float> b) {
     return r;
 }
 
-template <int R, int C, int MODE, int NTS, int S>
+template <int R, int C, int MODE, int NTS, int S, int SW = 0>
 __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds, cx<f2>* vp, int tid, uint64_t tile,
                                                    cx<float>* twp) {
     using C1 = cx<float>;
@@ -1378,12 +1406,12 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
                 const C1* row = in + bt * a.in_bstride + j + (uint64_t)b * rs;
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS)>(row + (uint64_t)(k * NB) * rs));
+                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS), SW>(row + (uint64_t)(k * NB) * rs));
             } else {
                 const C1* src = in + bt * a.in_bstride + j + ((uint64_t)b << les);
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS)>(src + ((uint64_t)(k * NB) << les)));
+                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << les)));
             }
         });
     }
@@ -1457,7 +1485,7 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
                 C1* dst = out + bt * a.out_bstride + pos + pad;
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    st_stream<nt_stores(NTS)>(dst + ((uint64_t)(k * NB) << lns), pk_get<u & 1>(vp[(u >> 1) * q + k]));
+                    st_stream<nt_stores(NTS), SW>(dst + ((uint64_t)(k * NB) << lns), pk_get<u & 1>(vp[(u >> 1) * q + k]));
             }
         });
     } else {
@@ -1501,7 +1529,7 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
                 }
             });
         }
-        pass_stages_packed<R, C, MODE, NTS, S + 1>(a, lds, vp, tid, tile, twp);
+        pass_stages_packed<R, C, MODE, NTS, S + 1, SW>(a, lds, vp, tid, tile, twp);
     }
 }
 
@@ -1522,51 +1550,76 @@ constexpr int first_tw_count() {
 //         each input v_r = z_q[j + r M/R] is evaluated from its P leaves
 // MODE 4 / 6: MODE 0 / 2 storing in bit-reversed order (PIFFT_OUT_BITREV)
 // NTS: non-temporal streaming of the data (nt_loads / nt_stores)
+// SW: the inverse plans' re/im swaps (ld_stream / st_stream) -- k_pass is SW =
+// 0, its twin k_pass_sw<..., SW> the same pass with SW's swaps.  Both kernels
+// are this one body around the shared __device__ pass_stages /
+// pass_stages_packed.  (The body is expanded in each kernel, not called:
+// behind one more __device__ __forceinline__ function taking the kernel's
+// PassArgs, a third of the forward instances compiled to different --
+// equivalent, differently scheduled -- code; expanded in place, the forward
+// code objects are byte for byte those from before the twins existed.)
+#ifdef PIFFT_WG_CLOCK
+#define PIFFT_WGC_ENTRY() \
+    if (a.wg_clock && tid == 0) a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x] = wall_clock64()
+#define PIFFT_WGC_EXIT()                                                        \
+    if (a.wg_clock) {                                                           \
+        __builtin_amdgcn_s_waitcnt(0); /* this thread's stores are done */      \
+        __syncthreads();                                                        \
+        if (tid == 0) {                                                         \
+            a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x + 1] = wall_clock64();      \
+            a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x + 2] = __smid();            \
+        }                                                                       \
+    }
+#else
+#define PIFFT_WGC_ENTRY() ((void)0)
+#define PIFFT_WGC_EXIT() ((void)0)
+#endif
+// (one tile per workgroup: a persistent tile loop -- 1, 2 or 4 resident
+// workgroups per CU walking the tiles -- measured 1.4-1.7x slower at 2^28 fp64,
+// DESIGN.md section 9.  Natural-order store, ilv_log: the P workers' tiles of
+// one line block run back to back, and on one XCD, log_xg >= log2 P, so the P
+// 16-B pieces of each output line meet in one L2 before it is written; 2^ltt
+// tiles per transform.)
+#define PIFFT_PASS_KERNEL_BODY(SW)                                                                                   \
+    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];                                       \
+    constexpr int Q = PassShape<R, VPT>::Q;                                                                          \
+    constexpr int TWN = first_tw_count<R, C, MODE, VPT>();                                                           \
+    cx<T> pre[pre_count<R, C, stage_mode(MODE), VPT>() > 0 ? pre_count<R, C, stage_mode(MODE), VPT>() : 1];          \
+    uint64_t tile = tile_of_block(blockIdx.x, a.log_xg, gridDim.x);                                                  \
+    T* lds = reinterpret_cast<T*>(pifft_smem);                                                                       \
+    const int tid = (int)threadIdx.x;                                                                                \
+    PIFFT_WGC_ENTRY();                                                                                               \
+    if constexpr (VPT == 32 && std::is_same_v<T, float> && PIFFT_PACK32) {                                           \
+        cx<f2> vp[PassShape<R, VPT>::Q / 2];                                                                         \
+        cx<float> twp[TWN];                                                                                          \
+        pass_stages_packed<R, C, MODE, NTS, 0, SW>(a, reinterpret_cast<float*>(pifft_smem), vp, tid, tile, twp);     \
+        (void)pre;                                                                                                   \
+        (void)lds;                                                                                                   \
+    } else {                                                                                                         \
+        if (a.ilv_log && a.log_lb >= (uint32_t)ilog2c(C)) {                                                          \
+            const uint32_t il = a.ilv_log, ltt = a.log_lb - (uint32_t)ilog2c(C);                                     \
+            const uint64_t q = tile & ((1ull << il) - 1), rest = tile >> il;                                         \
+            tile = ((rest >> ltt) << (il + ltt)) + (q << ltt) + (rest & ((1ull << ltt) - 1));                        \
+        }                                                                                                            \
+        cx<T> v[Q];                                                                                                  \
+        cx<T> twp[TWN];                                                                                              \
+        pass_stages<T, R, C, MODE, NTS, LP, 0, VPT, SW>(a, lds, v, pre, tid, tile, twp);                             \
+    }                                                                                                                \
+    PIFFT_WGC_EXIT()
+
 template <typename T, int R, int C, int MODE, int NTS, int LP, int VPT = 16>
 __global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<T, R, C, MODE, LP, VPT>()))
 void k_pass(PassArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];
-    constexpr int Q = PassShape<R, VPT>::Q;
-    constexpr int TWN = first_tw_count<R, C, MODE, VPT>();
-    cx<T> pre[pre_count<R, C, stage_mode(MODE), VPT>() > 0 ? pre_count<R, C, stage_mode(MODE), VPT>() : 1];
-    // one tile per workgroup: a persistent tile loop (1, 2 or 4 resident
-    // workgroups per CU walking the tiles) measured 1.4-1.7x slower at 2^28
-    // fp64
-    uint64_t tile = tile_of_block(blockIdx.x, a.log_xg, gridDim.x);
-    T* lds = reinterpret_cast<T*>(pifft_smem);
-    const int tid = (int)threadIdx.x;
-#ifdef PIFFT_WG_CLOCK
-    if (a.wg_clock && tid == 0) a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x] = wall_clock64();
-#endif
-    if constexpr (VPT == 32 && std::is_same_v<T, float> && PIFFT_PACK32) {
-        cx<f2> vp[PassShape<R, VPT>::Q / 2];
-        cx<float> twp[TWN];
-        pass_stages_packed<R, C, MODE, NTS, 0>(a, reinterpret_cast<float*>(pifft_smem), vp, tid, tile, twp);
-        (void)pre;
-        (void)lds;
-    } else {
-        if (a.ilv_log && a.log_lb >= (uint32_t)ilog2c(C)) {
-            // natural-order store: the P workers' tiles of one line block run
-            // back to back (and on one XCD, log_xg >= log2 P), so the P 16-B
-            // pieces of each output line meet in one L2 before it is written
-            const uint32_t il = a.ilv_log, ltt = a.log_lb - (uint32_t)ilog2c(C);  // 2^ltt tiles per transform
-            const uint64_t q = tile & ((1ull << il) - 1), rest = tile >> il;
-            tile = ((rest >> ltt) << (il + ltt)) + (q << ltt) + (rest & ((1ull << ltt) - 1));
-        }
-        cx<T> v[Q];
-        cx<T> twp[TWN];
-        pass_stages<T, R, C, MODE, NTS, LP, 0, VPT>(a, lds, v, pre, tid, tile, twp);
-    }
-#ifdef PIFFT_WG_CLOCK
-    if (a.wg_clock) {
-        __builtin_amdgcn_s_waitcnt(0);  // this thread's stores are done
-        __syncthreads();
-        if (tid == 0) {
-            a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x + 1] = wall_clock64();
-            a.wg_clock[PIFFT_WGC_WORDS * blockIdx.x + 2] = __smid();
-        }
-    }
-#endif
+    PIFFT_PASS_KERNEL_BODY(0);
+}
+
+// The swapping twin of k_pass<T, R, C, MODE, NTS, LP, VPT> for inverse plans:
+// the same pass with SW's swaps (1: loads of a.in, 2: stores to a.out, 3: both)
+template <typename T, int R, int C, int MODE, int NTS, int LP, int VPT, int SW>
+__global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<T, R, C, MODE, LP, VPT>()))
+void k_pass_sw(PassArgs a) {
+    static_assert(SW >= 1 && SW <= 3, "k_pass_sw: a swapping twin (the forward kernel is k_pass)");
+    PIFFT_PASS_KERNEL_BODY(SW);
 }
 
 // ---------------------------------------------------------------------------
@@ -1624,6 +1677,56 @@ __global__ __launch_bounds__(256) void k_tree(TreeArgs a) {
     }
     }  // grid-stride
 }
+// The swapping twin's body (inverse plans): k_tree's own statements with SW's
+// swaps.  The forward kernel above keeps its text: compiled as a call of this
+// body at SW = 0 it came out as different (equivalent) code -- the launch
+// geometry reads and the kernel-argument loads are lowered differently behind
+// a __device__ function -- and the forward code objects must not move.  Keep
+// the two in step.
+template <typename T, int L, int SW>
+__device__ __forceinline__ void tree_body(const TreeArgs& a, const uint32_t bdim, const uint32_t gdim) {
+    using C2 = cx<T>;
+    constexpr int V = 1 << L;
+    // grid-stride: the work-item count of one launch must stay below 2^32
+    for (uint64_t gid = (uint64_t)blockIdx.x * bdim + threadIdx.x; gid < a.total;
+         gid += (uint64_t)gdim * bdim) {
+    const uint32_t log_g = a.log_n - L;            // threads per transform = 2^log_g
+    const uint32_t log_d = a.log_n - a.t0 - L;     // D = stride between a thread's positions
+    const uint64_t g = gid & ((1ull << log_g) - 1), bt = gid >> log_g;
+    const uint64_t blk0 = g >> log_d, i = g & ((1ull << log_d) - 1);
+    const uint64_t base = blk0 << (a.log_n - a.t0);
+    const uint32_t log_w = a.log_p - a.t0 - L;     // workers below one level-(t0+L) block
+    const uint64_t q0 = a.q0, q1 = (uint64_t)a.q0 + a.nq;
+    const uint64_t w_lo = (blk0 << L) << log_w, w_hi = ((blk0 + 1) << L) << log_w;
+    if (w_hi <= q0 || w_lo >= q1) continue;  // no requested worker below this group
+    // no __restrict__ on src/dst: launches after the first of a multi-launch
+    // tree (log2 P > 4) run in place (src == dst == the plan's tree buffer);
+    // each thread reads and writes only its own 2^L positions
+    const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + base + i;
+    C2 v[V];
+#pragma unroll
+    for (int m = 0; m < V; m++) {
+        if constexpr (SW & 1) v[m] = sw_in<SW>(src[(uint64_t)m << log_d]);
+        else v[m] = src[(uint64_t)m << log_d];
+    }
+    tree_levels<T, L>(v, a.tw, i, log_d, a.t0, blk0, log_w, q0, q1);
+    C2* dst = static_cast<C2*>(a.out) + bt * a.out_bstride + (int64_t)(base + i) + a.out_shift;
+#pragma unroll
+    for (int m = 0; m < V; m++) {
+        const uint64_t wm = ((blk0 << L) + m) << log_w;
+        if (wm < q1 && wm + (1ull << log_w) > q0) {
+            if constexpr (SW & 2) dst[(uint64_t)m << log_d] = sw_out<SW>(v[m]);
+            else dst[(uint64_t)m << log_d] = v[m];
+        }
+    }
+    }  // grid-stride
+}
+// inverse plans: the tree launch that reads the caller's input (SW 1), writes
+// the caller's output (SW 2: M = 1, the last tree launch) or both (SW 3)
+template <typename T, int L, int SW>
+__global__ __launch_bounds__(256) void k_tree_sw(TreeArgs a) {
+    tree_body<T, L, SW>(a, blockDim.x, gridDim.x);
+}
 
 // The single launch of an all-worker tree (t0 = 0, all P = 2^L workers)
 // writing the worker-interleaved layout of the passes (PassArgs::wil):
@@ -1665,6 +1768,53 @@ __global__ __launch_bounds__(256) void k_tree_wil(TreeArgs a) {
         }
     }
 }
+// The swapping twin's body (inverse plans): k_tree_wil's own statements with SW's
+// swaps.  The forward kernel above keeps its text: compiled as a call of this
+// body at SW = 0 it came out as different (equivalent) code -- the launch
+// geometry reads and the kernel-argument loads are lowered differently behind
+// a __device__ function -- and the forward code objects must not move.  Keep
+// the two in step.
+template <typename T, int L, int SW>
+__device__ __forceinline__ void tree_wil_body(const TreeArgs& a, const uint32_t gdim) {
+    using C2 = cx<T>;
+    constexpr int V = 1 << L;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];
+    C2* stage = reinterpret_cast<C2*>(pifft_smem);
+    const uint32_t log_d = a.log_n - L;  // 2^log_d = M threads per transform
+    const uint64_t nblk = (a.total + 255) / 256;
+    // (block-uniform loop: every thread of a block reaches the barriers)
+    for (uint64_t blk = blockIdx.x; blk < nblk; blk += gdim) {
+        const uint64_t g0 = blk * 256, gid = g0 + threadIdx.x;
+        const uint64_t g = gid < a.total ? gid : a.total - 1;
+        const uint64_t bt = g >> log_d, i = g & ((1ull << log_d) - 1);
+        const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + i;
+        C2 v[V];
+#pragma unroll
+        for (int m = 0; m < V; m++) {
+            if constexpr (SW & 1) v[m] = sw_in<SW>(src[(uint64_t)m << log_d]);
+            else v[m] = src[(uint64_t)m << log_d];
+        }
+        tree_levels<T, L>(v, a.tw, i, log_d, 0, 0, 0, 0, V);
+        __syncthreads();  // the previous round's reads of `stage` are done
+#pragma unroll
+        for (int m = 0; m < V; m++) stage[tree_wil_pad(threadIdx.x * V + m)] = v[m];
+        __syncthreads();
+        const uint64_t b0 = g0 >> log_d, i0 = g0 & ((1ull << log_d) - 1);
+        C2* dst = static_cast<C2*>(a.out) + b0 * a.out_bstride + (i0 << L);
+        const uint64_t nvalid = (a.total - g0 < 256 ? a.total - g0 : 256) * V;
+#pragma unroll
+        for (int k = 0; k < V; k++) {
+            const uint32_t idx = (uint32_t)k * 256 + threadIdx.x;
+            if (idx < nvalid) dst[idx] = stage[tree_wil_pad(idx)];
+        }
+    }
+}
+// inverse plans (SW 1: it reads the caller's input; its output feeds the passes)
+template <typename T, int L, int SW>
+__global__ __launch_bounds__(256) void k_tree_wil_sw(TreeArgs a) {
+    static_assert(SW == 1, "k_tree_wil never writes the caller's output");
+    tree_wil_body<T, L, SW>(a, gridDim.x);
+}
 
 // ---------------------------------------------------------------------------
 // slice-major -> natural order: out[bt N + bitrev_P(q) + P k] = in[bt N + q M + k]
@@ -1682,6 +1832,35 @@ __global__ __launch_bounds__(256) void k_interleave(const cx<T>* __restrict__ in
         const uint32_t q = log_p ? (__builtin_bitreverse32(rr) >> (32 - log_p)) : 0u;
         out[gid] = in[bt * n + ((uint64_t)q << (log_n - log_p)) + k];
     }
+}
+// The swapping twin's body (inverse plans): k_interleave's own statements with SW's
+// swaps.  The forward kernel above keeps its text: compiled as a call of this
+// body at SW = 0 it came out as different (equivalent) code -- the launch
+// geometry reads and the kernel-argument loads are lowered differently behind
+// a __device__ function -- and the forward code objects must not move.  Keep
+// the two in step.
+template <typename T, int SW>
+__device__ __forceinline__ void interleave_body(const cx<T>* __restrict__ in, cx<T>* __restrict__ out, uint64_t total,
+                                                uint32_t log_n, uint32_t log_p, const uint32_t bdim,
+                                                const uint32_t gdim) {
+    const uint64_t n = 1ull << log_n;
+    for (uint64_t gid = (uint64_t)blockIdx.x * bdim + threadIdx.x; gid < total;
+         gid += (uint64_t)gdim * bdim) {
+        const uint64_t bt = gid >> log_n, o = gid & (n - 1);
+        const uint64_t k = o >> log_p;
+        const uint32_t rr = (uint32_t)(o & ((1ull << log_p) - 1));
+        const uint32_t q = log_p ? (__builtin_bitreverse32(rr) >> (32 - log_p)) : 0u;
+        if constexpr (SW & 2) out[gid] = sw_out<SW>(in[bt * n + ((uint64_t)q << (log_n - log_p)) + k]);
+        else out[gid] = in[bt * n + ((uint64_t)q << (log_n - log_p)) + k];
+    }
+}
+// inverse plans: the interleave launch writes the caller's output (SW 2)
+template <typename T, int SW>
+__global__ __launch_bounds__(256) void k_interleave_sw(const cx<T>* __restrict__ in,
+                                                       cx<T>* __restrict__ out, uint64_t total,
+                                                       uint32_t log_n, uint32_t log_p) {
+    static_assert(SW == 2, "k_interleave never reads the caller's input");
+    interleave_body<T, SW>(in, out, total, log_n, log_p, blockDim.x, gridDim.x);
 }
 
 // The same through an LDS tile of all P slices x K = 2048/P consecutive k
@@ -1723,6 +1902,51 @@ __global__ __launch_bounds__(256) void k_interleave_tile(const cx<T>* __restrict
         }
         (void)P;
     }
+}
+// The swapping twin's body (inverse plans): k_interleave_tile's own statements with SW's
+// swaps.  The forward kernel above keeps its text: compiled as a call of this
+// body at SW = 0 it came out as different (equivalent) code -- the launch
+// geometry reads and the kernel-argument loads are lowered differently behind
+// a __device__ function -- and the forward code objects must not move.  Keep
+// the two in step.
+template <typename T, int SW>
+__device__ __forceinline__ void interleave_tile_body(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
+                                                     uint64_t total, uint32_t log_n, uint32_t log_p,
+                                                     const uint32_t gdim) {
+    __shared__ cx<T> tile[IL_TILE + IL_TILE / 16];
+    const uint32_t log_k = 11 - log_p;  // K = 2048 / P
+    const uint32_t log_m = log_n - log_p;
+    const uint64_t ntiles = total >> 11;
+    const uint32_t P = 1u << log_p;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gdim) {
+        const uint64_t e0 = t << 11;  // first output of the tile
+        const uint64_t bt = e0 >> log_n, k0 = (e0 & ((1ull << log_n) - 1)) >> log_p;
+        const cx<T>* src = in + (bt << log_n) + k0;
+        __syncthreads();  // the previous tile's reads are done
+#pragma unroll
+        for (int i = 0; i < IL_TILE / 256; i++) {
+            const uint32_t e = threadIdx.x + i * 256;
+            const uint32_t q = e >> log_k, k = e & ((1u << log_k) - 1);
+            const uint32_t r = log_p ? (__builtin_bitreverse32(q) >> (32 - log_p)) : 0u;
+            const uint32_t o = (k << log_p) + r;  // natural position within the tile
+            tile[o + (o >> 4)] = src[((uint64_t)q << log_m) + k];
+        }
+        __syncthreads();
+        cx<T>* dst = out + e0;
+#pragma unroll
+        for (int i = 0; i < IL_TILE / 256; i++) {
+            const uint32_t o = threadIdx.x + i * 256;
+            if constexpr (SW & 2) dst[o] = sw_out<SW>(tile[o + (o >> 4)]);
+            else dst[o] = tile[o + (o >> 4)];
+        }
+        (void)P;
+    }
+}
+template <typename T, int SW>
+__global__ __launch_bounds__(256) void k_interleave_tile_sw(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
+                                                            uint64_t total, uint32_t log_n, uint32_t log_p) {
+    static_assert(SW == 2, "k_interleave_tile never reads the caller's input");
+    interleave_tile_body<T, SW>(in, out, total, log_n, log_p, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------

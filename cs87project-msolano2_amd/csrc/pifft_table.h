@@ -12,6 +12,36 @@ struct PassKernel {
     int vpt;  // values per thread (16; 32 for the packed fp32 passes)
 };
 
+// A swapping twin of a k_pass instance, for inverse plans (PIFFT_INVERSE):
+// k_pass_sw<..., SW> of the forward instance {prec, R, C, mode, nts, lp, vpt}.
+// The twins live in tables of their own (pifft_passes.hip compiled with
+// -DPIFFT_TWINS); the registry of forward instances above does not know them.
+struct TwinKernel {
+    int prec, R, C, mode, nts, lp, vpt;
+    int sw;          // 1: swaps the loads of PassArgs::in, 2: the stores to PassArgs::out, 3: both
+    const void* fn;  // null: no inverse plan launches this (instance, sw) -- not compiled
+};
+
+// The twins an inverse plan can reach, by the pass MODE's place in a plan:
+//   0 / 4 (single pass): the only launch (3), or the last one after a tree (2);
+//   1 / 3 (first pass, fused one-worker tree): reads the caller's input (1);
+//   11 (all-worker tree fused into the first pass): 1, and both (3) in its
+//       one-launch form, the tile of C = P lines;
+//   2 / 6 / 10 (later passes): the last pass writes the caller's output (2).
+constexpr bool twin_reachable(int mode, int C, int lp, int sw) {
+    return (mode == 0 || mode == 4)   ? (sw == 3 || sw == 2)
+           : (mode == 1 || mode == 3) ? sw == 1
+           : mode == 11               ? (sw == 1 || (sw == 3 && C == (1 << lp)))
+                                      : sw == 2;
+}
+// the (up to) two SW values of a MODE's twins, in table order
+constexpr int twin_sw(int mode, int slot) {
+    return (mode == 0 || mode == 4)   ? (slot ? 2 : 3)
+           : (mode == 1 || mode == 3) ? (slot ? 0 : 1)
+           : mode == 11               ? (slot ? 3 : 1)
+                                      : (slot ? 0 : 2);
+}
+
 }  // namespace pifft
 
 #define PIFFT_NPART 8

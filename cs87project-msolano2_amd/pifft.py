@@ -22,6 +22,7 @@ F32, F64 = 32, 64
 OUT_NATURAL, OUT_SLICES, OUT_BITREV = 0, 1, 2
 PROFILE_ALL, PROFILE_SAMPLED = 0, 1
 SEPARATE_TREE = 4  # flag bit: the tree never fused into the first pass (CLI -u)
+INVERSE = 8  # flag bit: the unnormalised inverse transform, e^{+2 pi i nk/N} (CLI -i)
 KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass"}
 MAX_LAUNCH_INFO = 256  # PIFFT_MAX_LAUNCH_INFO (include/pifft.h)
 
@@ -113,7 +114,7 @@ _lib = None
 
 def build(quiet: bool = True) -> None:
     """hipcc --offload-arch=gfx950 -> libpifft.so, gcc -> the pifft CLI (in-tree)."""
-    subprocess.run(["make", "-j8", "-C", HERE, "all"], check=True,
+    subprocess.run(["make", "-j16", "-C", HERE, "all"], check=True,
                    stdout=subprocess.DEVNULL if quiet else None)
 
 
@@ -171,9 +172,9 @@ class Plan:
 
     def __init__(self, n: int, workers: int = 1, batch: int = 1, prec: int = F64, *,
                  first: int = 0, count: int | None = None, device: int | None = None,
-                 flags: int | None = None):
+                 flags: int | None = None, inverse: bool = False):
         h = _P()
-        if count is None and device is None and flags is None and first == 0:
+        if count is None and device is None and flags is None and first == 0 and not inverse:
             _check(lib().pifft_plan_create(ctypes.byref(h), n, workers, batch, prec), "pifft_plan_create")
         else:
             count = workers if count is None else count
@@ -182,6 +183,8 @@ class Plan:
                 flags = OUT_NATURAL if count == workers else OUT_SLICES
             elif flags == SEPARATE_TREE:
                 flags |= OUT_NATURAL if count == workers else OUT_SLICES
+            if inverse:
+                flags |= INVERSE
             _check(lib().pifft_plan_create_slices(ctypes.byref(h), n, workers, first, count, batch, prec,
                                                   device, flags), "pifft_plan_create_slices")
         self._h = h
@@ -283,6 +286,7 @@ def describe_info(i: PlanInfo) -> dict:
         "launch_mode": list(i.launch_mode[: min(nl, MAX_LAUNCH_INFO)]),
         "vpt": list(i.vpt[: i.num_passes]),
         "worker_interleaved": bool(i.layout & 1), "natural_store": bool(i.layout & 2),
+        "inverse": bool(i.flags & INVERSE),
     }
 
 
@@ -308,13 +312,16 @@ def instances_found() -> list:
 
 
 def dry_run_instances(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, first: int = 0,
-                      count: int | None = None, flags: int | None = None) -> list:
+                      count: int | None = None, flags: int | None = None, inverse: bool = False) -> list:
     """The registry index of each launch's k_pass instance (-1: a tree or
     interleave launch) of the plan pifft_plan_dry_run describes (flags as
-    dry_run: natural order for all workers, else slice-major)."""
+    dry_run: natural order for all workers, else slice-major).  inverse: the
+    forward instance each swapping twin of the inverse plan derives from."""
     count = workers if count is None else count
     if flags is None:
         flags = OUT_NATURAL if count == workers else OUT_SLICES
+    if inverse:
+        flags |= INVERSE
     ids = (ctypes.c_int32 * MAX_LAUNCH_INFO)()
     nl = lib().pifft_plan_dry_run_instances(n, workers, first, count, batch, prec, flags, ids, MAX_LAUNCH_INFO)
     if nl < 0:
@@ -323,11 +330,13 @@ def dry_run_instances(n: int, workers: int = 1, batch: int = 1, prec: int = F64,
 
 
 def dry_run(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, first: int = 0,
-            count: int | None = None, flags: int | None = None) -> dict:
+            count: int | None = None, flags: int | None = None, inverse: bool = False) -> dict:
     """The plan that would be built, without a device (host planning only)."""
     count = workers if count is None else count
     if flags is None:
         flags = OUT_NATURAL if count == workers else OUT_SLICES
+    if inverse:
+        flags |= INVERSE
     info = PlanInfo()
     _check(lib().pifft_plan_dry_run(n, workers, first, count, batch, prec, flags, ctypes.byref(info)),
            "pifft_plan_dry_run")

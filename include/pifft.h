@@ -21,6 +21,10 @@
  * -Dfloat=double).  Transform: unnormalised forward DFT
  * X[k] = sum_n x[n] e^{-2 pi i nk/N}, natural-order input and output (the
  * reference's `out` after its bit-reversed scatter, CPU.c:496-499).
+ * A PIFFT_INVERSE plan computes the unnormalised inverse DFT instead,
+ * y[n] = sum_k X[k] e^{+2 pi i nk/N} (no 1/N: the caller's, as FFTW's and
+ * rocFFT's backward transforms), natural-order input; worker q of P then owns
+ * the output samples bitrev_{log2 P}(q) + P*k in the same output orders.
  *
  * Workers: worker q of P owns the natural-order output bins
  *   bitrev_{log2 P}(q) + P*k,  k < N/P
@@ -66,6 +70,21 @@ extern "C" {
                                reference's tm_funnel (CPU.c:414-448) -- the column
                                its cost-law fit regresses on n(p-1)/p
                                (analyze-results.R:56); CLI -u                  */
+
+#define PIFFT_INVERSE 8 /* flag bit, OR-ed with one of the orders above (and optionally
+                               PIFFT_SEPARATE_TREE): the unnormalised inverse transform
+                               y[n] = sum_k X[k] e^{+2 pi i nk/N}.  With swap(a + bi) =
+                               b + ai, IDFT(x) = swap(DFT(swap(x))): the plan is the
+                               forward plan of the same arguments -- same launches,
+                               bytes, tables and workspace -- whose launch reading
+                               d_in swaps re/im of what it loads and whose launch
+                               writing d_out swaps what it stores (compile-time twins
+                               of those two kernels; register renames).  The result
+                               equals swap(forward(swap(x))) bit for bit.  Every
+                               entry point that runs a plan's launches takes inverse
+                               plans; the plans of one pifft_execute_group or
+                               pifft_allgather call must share the direction, and
+                               pifft_tree_device takes forward plans only.  CLI -i */
 
 typedef struct pifft_plan pifft_plan;
 
@@ -138,14 +157,17 @@ int pifft_plan_create(pifft_plan** plan, uint64_t n, uint32_t workers, uint32_t 
  * multi-GPU job; the reference's run_thread for each of those Pi).  count must
  * be a power of two dividing first.  flags: PIFFT_OUT_NATURAL (only when
  * count == workers), PIFFT_OUT_SLICES or PIFFT_OUT_BITREV, optionally with
- * PIFFT_SEPARATE_TREE. */
+ * PIFFT_SEPARATE_TREE and / or PIFFT_INVERSE (pifft_plan_create is always
+ * forward). */
 int pifft_plan_create_slices(pifft_plan** plan, uint64_t n, uint32_t workers, uint32_t first,
                              uint32_t count, uint32_t batch, int prec, int device, int flags);
 
 void pifft_plan_destroy(pifft_plan* plan);
 
 /* The plan pifft_plan_create_slices would build, described without touching
- * a device or allocating (host-side planning only; device = -1 in info). */
+ * a device or allocating (host-side planning only; device = -1 in info).  An
+ * inverse plan's info equals the forward plan's in every field but flags and
+ * launch_fn (its first and last launches are kernels of their own). */
 int pifft_plan_dry_run(uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch,
                        int prec, int flags, pifft_plan_info* info);
 
@@ -157,7 +179,8 @@ int pifft_plan_get_info(const pifft_plan* plan, pifft_plan_info* info);
  * to desc[0..6].  pifft_plan_dry_run_instances plans as pifft_plan_dry_run does
  * and writes, for each launch i < min(launches, max_ids), the instance index of
  * its k_pass kernel (-1 for tree and interleave launches); it returns the
- * number of launches, or -1.  pifft_instance_found(i) is 1 once the planner
+ * number of launches, or -1 (for an inverse plan: the forward instance each
+ * swapping twin derives from; the twins are not in the registry).  pifft_instance_found(i) is 1 once the planner
  * has found instance i in this process (it probes instances to choose between
  * plans, so a plan depends on every instance it found, launched or not), 0 if
  * not, -1 for an index out of range.  tests/test_instances.py checks with
@@ -307,7 +330,8 @@ int pifft_interleave_device(const void* d_slices, void* d_out, uint64_t n, uint3
 
 /* Tree ("funnel") stage only, for parity checks: writes worker q's N/P segment
  * after the log2 P half-butterfly stages (the reference's tmp_in segment after
- * CPU.c:419-448) for the plan's workers, slice-major. */
+ * CPU.c:419-448) for the plan's workers, slice-major.  Forward plans only
+ * (-1 on a PIFFT_INVERSE plan). */
 int pifft_tree_device(pifft_plan* plan, const void* d_in, void* d_seg, void* stream);
 
 #ifdef __cplusplus
