@@ -8,6 +8,7 @@
 //   passes  : Z -> ... -> Z'   Stockham passes of the N/P-point local FFT,
 //             each an LDS-resident R-point sub-FFT over C adjacent lines
 //   [interleave: slice-major -> natural order, whole transform on one GPU]
+//   [real plans: the N/2-point chain above plus one fix-up launch (create_real, pifft_real.h)]
 //
 // Buffers ping-pong between the caller's output and one plan-owned workspace.
 // Twiddles are host-built tables in HBM (w_R per pass, two-level w_M and w_N;
@@ -18,6 +19,7 @@
 #endif
 #include "pifft_gather.h"
 #include "pifft_kernels.h"
+#include "pifft_real.h"
 #include "pifft_table.h"
 #include "../../include/pifft.h"
 
@@ -238,8 +240,9 @@ const void* find_aux_twin(const void* fn, int sw) {
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
-enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4 };
-enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, NBUF = 4 };
+enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, STEP_R2C_POST = 5, STEP_C2R_PRE = 6 };
+// BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real)
+enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, NBUF = 5 };
 
 struct Step {
     int kind = 0;
@@ -254,6 +257,7 @@ struct Step {
     TreeArgs ta{};
     uint64_t il_total = 0;
     uint32_t il_log_n = 0, il_log_p = 0;
+    RealArgs ra{};  // STEP_R2C_POST / STEP_C2R_PRE
     uint64_t bytes = 0;
 };
 
@@ -271,6 +275,13 @@ struct pifft_plan {
     bool wil = false;     // worker-interleaved layout (PassArgs::wil, MODE | 8 passes)
     bool separate_tree = false;  // PIFFT_SEPARATE_TREE: never fuse the tree into a pass
     bool inverse = false;        // PIFFT_INVERSE: the first / last launch swap re/im (make_inverse)
+    // pifft_plan_create_real: 0 complex, 1 R2C, 2 C2R.  Every field above and
+    // below describes the inner N/2-point complex plan (n = real_n / 2)
+    int real = 0;
+    uint64_t real_n = 0;
+    size_t bytes_z = 0;
+    void* d_rtw = nullptr;  // the fix-up step's two-level w_N table
+    size_t rtw_bytes = 0;
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -693,6 +704,7 @@ void release(pifft_plan* p) {
     for (int b = BUF_W; b < NBUF; b++)
         if (p->buf[b]) (void)hipFree(p->buf[b]);
     if (p->d_tw) (void)hipFree(p->d_tw);
+    if (p->d_rtw) (void)hipFree(p->d_rtw);
     if (p->d_hin) (void)hipFree(p->d_hin);
     if (p->d_hout) (void)hipFree(p->d_hout);
     if (p->d_gather) (void)hipFree(p->d_gather);
@@ -1326,6 +1338,102 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
     return 0;
 }
 
+// Real-input plans (pifft_plan_create_real; kernels and formulas in
+// pifft_real.h).  The N reals are the H = N/2 complex values z[n] = x[2n] +
+// i x[2n+1] as they lie in memory, so the plan is the complex plan build_plan
+// makes for (H, P, all workers, natural order) -- untouched, whatever it
+// chooses for that shape -- plus one streaming launch:
+//   R2C: [inner forward chain: d_in -> Z] [k_r2c_post: Z -> d_out]
+//   C2R: [k_c2r_pre: d_in -> Z] [inner inverse chain (make_inverse): Z -> d_out]
+// Z (BUF_Z, batch x H values) is plan-owned: the inner chain of an R2C plan
+// uses it wherever the complex plan uses the caller's output (its last store
+// and, in multi-pass plans, a ping-pong stage), that of a C2R plan where the
+// complex plan reads the caller's input; d_in is never written.  Bins k and
+// H - k belong to different workers (residues r and -r mod P), so a real plan
+// always holds all P workers.
+int create_real(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t batch, int prec, int device, int direction,
+                bool dry = false) {
+    if (!out) return fail("plan pointer is NULL");
+    *out = nullptr;
+    if (n < 4 || !is_pow2(n)) return fail("Invalid input size (a real plan needs 2^i reals, i > 1)");
+    if (workers == 0 || !is_pow2(workers)) return fail("Invalid number of procs (should be 2^i for i>0)");
+    if (workers > n / 2) return fail("More processors than inputs! (a real plan splits its n/2-point transform)");
+    if (batch == 0) return fail("batch must be >= 1");
+    if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
+    if (direction != PIFFT_REAL_FORWARD && direction != PIFFT_REAL_INVERSE)
+        return fail("direction must be PIFFT_REAL_FORWARD or PIFFT_REAL_INVERSE");
+    const bool c2r = direction == PIFFT_REAL_INVERSE;
+    const uint64_t H = n / 2;
+    pifft_plan* p = nullptr;
+    if (create(&p, H, workers, 0, workers, batch, prec, device, PIFFT_OUT_NATURAL | (c2r ? PIFFT_INVERSE : 0), dry))
+        return -1;
+    p->real = c2r ? 2 : 1;
+    p->real_n = n;
+    p->bytes_z = (size_t)batch * H * p->esz;
+    // w_N^k, k <= N/4, two-level at every size: 2^h ~ sqrt N entries per
+    // level (256 KiB each at fp64 2^28), against N/4 + 1 of a direct table
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    const TwoLevel tw = two_level(tb, n);
+    tb.align();
+    p->rtw_bytes = tb.size();
+    DeviceGuard g(dry ? -1 : device);
+    if (!dry) {
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        if (hipMalloc(&p->buf[BUF_Z], p->bytes_z) != hipSuccess || hipMalloc(&p->d_rtw, p->rtw_bytes) != hipSuccess ||
+            hipMemcpy(p->d_rtw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipEventCreateWithFlags(&ev[0], kTimingEventFlags) != hipSuccess ||
+            hipEventCreateWithFlags(&ev[1], kTimingEventFlags) != hipSuccess) {
+            const hipError_t err = hipGetLastError();
+            for (auto e : ev)
+                if (e) (void)hipEventDestroy(e);
+            const size_t want = p->bytes_z;
+            release(p);
+            return fail("real plan: allocating the staging buffer (%zu bytes), table or events failed: %s", want,
+                        hipGetErrorString(err));
+        }
+        p->ev.push_back(ev[0]);  // the added launch's start and stop
+        p->ev.push_back(ev[1]);
+    }
+    Step s;
+    s.kind = c2r ? STEP_C2R_PRE : STEP_R2C_POST;
+    s.fn = prec == PIFFT_F64 ? (c2r ? (const void*)&k_c2r_pre<double> : (const void*)&k_r2c_post<double>)
+                             : (c2r ? (const void*)&k_c2r_pre<float> : (const void*)&k_r2c_post<float>);
+    s.ra.tw_lo = dry ? nullptr : (const void*)((const char*)p->d_rtw + tw.lo);
+    s.ra.tw_hi = dry ? nullptr : (const void*)((const char*)p->d_rtw + tw.hi);
+    s.ra.tw_h = tw.h;
+    s.ra.batch = batch;
+    s.ra.h = H;
+    s.ra.units = prec == PIFFT_F64 ? real_units<double>(H) : real_units<float>(H);
+    s.block = dim3(256);
+    s.grid = dim3(stride_grid((uint64_t)batch * s.ra.units));
+    const uint64_t threads = (uint64_t)s.grid.x * 256;
+    s.ra.step_rows = threads / s.ra.units;
+    s.ra.step_units = threads % s.ra.units;
+    s.bytes = (uint64_t)batch * (2 * H + 1) * p->esz;
+    if (c2r) {
+        s.src = BUF_IN;
+        s.dst = BUF_Z;
+        for (Step& t : p->steps)
+            if (t.src == BUF_IN) t.src = BUF_Z;
+        p->steps.insert(p->steps.begin(), s);
+    } else {
+        for (Step& t : p->steps) {
+            if (t.src == BUF_OUT) t.src = BUF_Z;
+            if (t.dst == BUF_OUT) t.dst = BUF_Z;
+        }
+        s.src = BUF_Z;
+        s.dst = BUF_OUT;
+        p->steps.push_back(s);
+    }
+    p->tree_only.clear();  // (pifft_tree_device refuses real plans)
+    *out = p;
+    return 0;
+}
+
+const char* kRealOnly = "real plans (pifft_plan_create_real) run through pifft_execute_device, "
+                        "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
+
 // One launch.  With events (e0, e1): hipExtLaunchKernel binds them to the
 // kernel's own dispatch (its start and end timestamps, what rocprofv3 reports
 // as the kernel's duration) -- no marker packet between launches.  Marker
@@ -1334,7 +1442,7 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
 // (round-2 verdict); kernel-bound events add nothing to the stream.
 int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hipStream_t st,
                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    void* base[NBUF] = {const_cast<void*>(d_in), d_out, p->buf[BUF_W], p->buf[BUF_TA]};
+    void* base[NBUF] = {const_cast<void*>(d_in), d_out, p->buf[BUF_W], p->buf[BUF_TA], p->buf[BUF_Z]};
     const char* src = (const char*)base[s.src] + s.src_off * p->esz;
     char* dst = (char*)base[s.dst] + s.dst_off * p->esz;
     auto go = [&](void** args, size_t lds) {
@@ -1369,6 +1477,15 @@ int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hip
             uint64_t total = s.il_total;
             uint32_t ln = s.il_log_n, lpp = s.il_log_p;
             void* args[] = {&in, &o, &total, &ln, &lpp};
+            e = go(args, 0);
+            break;
+        }
+        case STEP_R2C_POST:
+        case STEP_C2R_PRE: {
+            RealArgs a = s.ra;
+            a.in = src;
+            a.out = dst;
+            void* args[] = {&a};
             e = go(args, 0);
             break;
         }
@@ -1702,6 +1819,23 @@ int pifft_plan_dry_run(uint64_t n, uint32_t workers, uint32_t first, uint32_t co
     return rc;
 }
 
+int pifft_plan_create_real(pifft_plan** plan, uint64_t n, uint32_t workers, uint32_t batch, int prec, int device,
+                           int direction) {
+    return create_real(plan, n, workers, batch, prec, device, direction);
+}
+
+int pifft_plan_dry_run_real(uint64_t n, uint32_t workers, uint32_t batch, int prec, int direction,
+                            pifft_plan_info* info) {
+    if (!info) return fail("info is NULL");
+    pifft_plan* p = nullptr;
+    if (create_real(&p, n, workers, batch, prec, -1, direction, true)) return -1;
+    const int rc = pifft_plan_get_info(p, info);
+    release(p);
+    return rc;
+}
+
+int pifft_plan_is_real(const pifft_plan* plan) { return plan ? plan->real : -1; }
+
 int pifft_instance_count(void) { return (int)pass_kernels().size(); }
 
 int pifft_instance_desc(int i, int32_t* desc) {
@@ -1748,6 +1882,13 @@ int pifft_plan_get_info(const pifft_plan* p, pifft_plan_info* info) {
     info->in_elems = (uint64_t)p->batch * p->n;
     info->out_elems = out_elems(p);
     info->workspace_bytes = p->bytes_w + p->bytes_ta + p->tw_bytes;
+    if (p->real) {  // n: the real length; buffers in complex elements of the precision
+        const uint64_t H = p->n;
+        info->n = p->real_n;
+        info->in_elems = (uint64_t)p->batch * (p->real == 1 ? H : H + 1);
+        info->out_elems = (uint64_t)p->batch * (p->real == 1 ? H + 1 : H);
+        info->workspace_bytes += p->bytes_z + p->rtw_bytes;
+    }
     info->layout = (p->wil ? 1 : 0) | (p->ilv ? 2 : 0);
     info->num_launches = (int)p->steps.size();
     info->num_passes = p->npasses;
@@ -1879,6 +2020,7 @@ int pifft_debug_wg_clock(pifft_plan* p, int launch, const void* d_in, void* d_ou
 int pifft_plan_tune_workspace(pifft_plan* p, const void* d_in, void* d_out, void* stream, int tries,
                               float* best_ms) {
     if (check_buffers(p, d_in, d_out)) return -1;
+    if (p->real) return fail("pifft_plan_tune_workspace: %s", kRealOnly);
     if (tries < 1) return fail("tries must be >= 1");
     DeviceGuard g(p->device);
     hipStream_t st = (hipStream_t)stream;
@@ -2011,6 +2153,7 @@ int pifft_execute_device_timed(pifft_plan* p, const void* d_in, void* d_out, voi
 }
 
 int pifft_execute(pifft_plan* p, const void* host_in, void* host_out, double* ms1, double* ms2) {
+    if (p && p->real) return fail("pifft_execute: %s", kRealOnly);
     return pifft_execute_group(&p, 1, host_in, host_out, ms1, ms2);
 }
 
@@ -2020,6 +2163,7 @@ int pifft_execute_group(pifft_plan** plans, int np, const void* host_in, void* h
     if (!host_in) return fail("host_in is NULL");
     for (int i = 0; i < np; i++) {
         if (!plans[i]) return fail("plan %d is NULL", i);
+        if (plans[i]->real) return fail("pifft_execute_group: %s", kRealOnly);
         if (plans[i]->n != plans[0]->n || plans[i]->batch != plans[0]->batch ||
             plans[i]->prec != plans[0]->prec)
             return fail("plans of a group must share n, batch and precision");
@@ -2149,6 +2293,7 @@ int pifft_execute_group_kernel_times(pifft_plan** plans, int np, double* ms1, do
     if (!plans || np <= 0) return fail("no plans");
     for (int i = 0; i < np; i++) {
         if (!plans[i]) return fail("plan %d is NULL", i);
+        if (plans[i]->real) return fail("pifft_execute_group_kernel_times: %s", kRealOnly);
         if (!plans[i]->d_hin || !plans[i]->d_hout) return fail("plan %d: no staged input (call pifft_execute_group first)", i);
     }
     for (int i = 0; i < np; i++) {
@@ -2200,11 +2345,14 @@ int pifft_interleave_device(const void* d_slices, void* d_out, uint64_t n, uint3
 
 int pifft_allgather(pifft_plan* const* plans, int nplans, const void* const* d_slices, void* const* d_natural,
                     double* ms) {
+    for (int i = 0; plans && i < nplans; i++)
+        if (plans[i] && plans[i]->real) return fail("pifft_allgather: %s", kRealOnly);
     return gather_group(plans, nplans, d_slices, d_natural, ms);
 }
 
 int pifft_tree_device(pifft_plan* p, const void* d_in, void* d_seg, void* stream) {
     if (check_buffers(p, d_in, d_seg)) return -1;
+    if (p->real) return fail("pifft_tree_device: %s", kRealOnly);
     if (p->inverse) return fail("pifft_tree_device: forward plans only (the reference's tree)");
     DeviceGuard g(p->device);
     hipStream_t st = (hipStream_t)stream;  // NULL = the default stream

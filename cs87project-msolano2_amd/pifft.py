@@ -23,7 +23,8 @@ OUT_NATURAL, OUT_SLICES, OUT_BITREV = 0, 1, 2
 PROFILE_ALL, PROFILE_SAMPLED = 0, 1
 SEPARATE_TREE = 4  # flag bit: the tree never fused into the first pass (CLI -u)
 INVERSE = 8  # flag bit: the unnormalised inverse transform, e^{+2 pi i nk/N} (CLI -i)
-KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass"}
+REAL_FORWARD, REAL_INVERSE = 0, 1  # pifft_plan_create_real directions: R2C, C2R
+KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r"}
 MAX_LAUNCH_INFO = 256  # PIFFT_MAX_LAUNCH_INFO (include/pifft.h)
 
 
@@ -76,6 +77,11 @@ _SIGS = {
     "pifft_plan_dry_run": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(PlanInfo)]),
     "pifft_plan_get_info": (ctypes.c_int, [_P, ctypes.POINTER(PlanInfo)]),
+    "pifft_plan_create_real": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pifft_plan_dry_run_real": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                               ctypes.c_int, ctypes.POINTER(PlanInfo)]),
+    "pifft_plan_is_real": (ctypes.c_int, [_P]),
     "pifft_plan_kernel_name": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     "pifft_execute_device": (ctypes.c_int, [_P, _P, _P, _P]),
     "pifft_execute_device_timed": (ctypes.c_int, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_float),
@@ -202,6 +208,10 @@ class Plan:
     def describe(self) -> dict:
         return describe_info(self.info)
 
+    def is_real(self) -> int:
+        """pifft_plan_is_real: 0 a complex plan, 1 R2C, 2 C2R."""
+        return lib().pifft_plan_is_real(self._h)
+
     def kernel_name(self, launch: int) -> str:
         """Demangled kernel function of one launch (as rocprofv3 names it)."""
         buf = ctypes.create_string_buffer(512)
@@ -272,6 +282,27 @@ class Plan:
             pass
 
 
+class RealPlan(Plan):
+    """A real-input transform of n samples (pifft_plan_create_real): R2C, n
+    reals -> n/2 + 1 bins, or with inverse=True C2R, n/2 + 1 bins -> n reals
+    (unnormalised: C2R(R2C(x)) = n x).  All `workers` on one device; runs
+    through the device-boundary methods (execute_device, execute_device_timed,
+    profile_*, launch_loop), the others raise PifftError."""
+
+    def __init__(self, n: int, workers: int = 1, batch: int = 1, prec: int = F64, *,
+                 device: int | None = None, inverse: bool = False):
+        h = _P()
+        _check(lib().pifft_plan_create_real(ctypes.byref(h), n, workers, batch, prec, 0 if device is None else device,
+                                            REAL_INVERSE if inverse else REAL_FORWARD), "pifft_plan_create_real")
+        self._h = h
+        self.info = self._info()
+
+
+def _real_kind(i: PlanInfo) -> int:
+    kinds = i.launch_kind[: min(i.num_launches, MAX_LAUNCH_INFO)]
+    return 1 if 5 in kinds else 2 if 6 in kinds else 0
+
+
 def describe_info(i: PlanInfo) -> dict:
     nl = i.num_launches
     return {
@@ -287,6 +318,7 @@ def describe_info(i: PlanInfo) -> dict:
         "vpt": list(i.vpt[: i.num_passes]),
         "worker_interleaved": bool(i.layout & 1), "natural_store": bool(i.layout & 2),
         "inverse": bool(i.flags & INVERSE),
+        "real": _real_kind(i),  # 0 complex, 1 R2C, 2 C2R (pifft_plan_is_real)
     }
 
 
@@ -340,6 +372,14 @@ def dry_run(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, first:
     info = PlanInfo()
     _check(lib().pifft_plan_dry_run(n, workers, first, count, batch, prec, flags, ctypes.byref(info)),
            "pifft_plan_dry_run")
+    return describe_info(info)
+
+
+def dry_run_real(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, inverse: bool = False) -> dict:
+    """The real plan that would be built (pifft_plan_dry_run_real), without a device."""
+    info = PlanInfo()
+    _check(lib().pifft_plan_dry_run_real(n, workers, batch, prec, REAL_INVERSE if inverse else REAL_FORWARD,
+                                         ctypes.byref(info)), "pifft_plan_dry_run_real")
     return describe_info(info)
 
 

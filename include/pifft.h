@@ -121,7 +121,7 @@ typedef struct pifft_plan_info {
     uint64_t launch_bytes[PIFFT_MAX_LAUNCH_INFO]; /* algorithmic bytes of each launch
                                   (read+write of the data, twiddle tables excluded) */
     int32_t launch_kind[PIFFT_MAX_LAUNCH_INFO]; /* 1 tree, 2 pass, 3 interleave, 4 tree fused
-                                  into a pass */
+                                  into a pass, 5 / 6 the R2C / C2R fix-up of a real plan */
     int32_t launch_fn[PIFFT_MAX_LAUNCH_INFO]; /* kernel of each launch: launches with the same id
                                   run the same kernel function (ids 0, 1, ... in order
                                   of first use) -- what rocprof aggregates per kernel */
@@ -172,6 +172,52 @@ int pifft_plan_dry_run(uint64_t n, uint32_t workers, uint32_t first, uint32_t co
                        int prec, int flags, pifft_plan_info* info);
 
 int pifft_plan_get_info(const pifft_plan* plan, pifft_plan_info* info);
+
+/* Real-input transforms (R2C / C2R, as FFTW's and rocFFT's): n real samples,
+ * n a power of two >= 4, H = n/2.  The n reals are the H complex values
+ * z[j] = x[2j] + i x[2j+1] as they lie in memory, so a real plan is the complex
+ * plan of (H, workers, all workers, natural order, batch, prec) -- the same
+ * launches as that plan's dry run describes -- plus one streaming launch and a
+ * plan-owned staging buffer of batch*H values (counted in workspace_bytes):
+ *
+ *   PIFFT_REAL_FORWARD (R2C): d_in holds batch rows of n reals (T x[n], T =
+ *     float or double: batch*H complex elements), d_out receives batch rows of
+ *     H+1 bins X[0..H] = sum_j x[j] e^{-2 pi i jk/n}, interleaved complex, row
+ *     stride H+1 (the bins k > H are conj X[n-k] and are not stored).  The
+ *     imaginary parts of X[0] and X[H] are exactly 0.  Launches: the forward
+ *     chain of the H-point plan, then the fix-up kernel (launch_kind 5) pairing
+ *     bins k and H-k.
+ *   PIFFT_REAL_INVERSE (C2R): d_in holds batch rows of H+1 bins (row stride
+ *     H+1), d_out receives batch rows of n reals y[j] = sum over the Hermitian
+ *     extension of X of X[k] e^{+2 pi i jk/n}: unnormalised, y = n x when
+ *     X = R2C(x) (no 1/n, as PIFFT_INVERSE).  The imaginary parts of X[0] and
+ *     X[H] are ignored (as numpy's irfft and FFTW do).  Launches: the fix-up
+ *     kernel (launch_kind 6), then the PIFFT_INVERSE chain of the H-point plan.
+ *
+ * workers: a power of two <= H; a real plan always holds all of them on one
+ * device (bins k and H-k belong to different workers).  d_in is never written;
+ * rows need the alignment of their complex type (hipMalloc's is enough for
+ * every row).  The info of a real plan: n = the real length, local_n = H /
+ * workers, flags = PIFFT_OUT_NATURAL (| PIFFT_INVERSE for C2R), in_elems and
+ * out_elems in complex elements of the plan's precision (R2C batch*H in,
+ * batch*(H+1) out; C2R the reverse), launch_bytes of the fix-up launch =
+ * batch*(2H+1) elements read plus written, num_passes / radix / lines / vpt /
+ * launch_mode the inner plan's.  The dry run takes no device.
+ *
+ * A real plan runs through the device-boundary entry points below that take
+ * one plan and device buffers, unchanged: execute_device, execute_device_timed,
+ * profile_start / profile_read, launch_loop, and plan_get_info,
+ * plan_kernel_name, plan_destroy.  The host-boundary and multi-plan entry
+ * points (execute, execute_group, execute_group_kernel_times, allgather),
+ * tree_device and plan_tune_workspace return -1 on a real plan.
+ * pifft_plan_is_real: 0 for a complex plan, 1 R2C, 2 C2R, -1 for NULL. */
+#define PIFFT_REAL_FORWARD 0 /* R2C: n reals -> n/2+1 bins */
+#define PIFFT_REAL_INVERSE 1 /* C2R: n/2+1 bins -> n reals */
+int pifft_plan_create_real(pifft_plan** plan, uint64_t n, uint32_t workers, uint32_t batch,
+                           int prec, int device, int direction);
+int pifft_plan_dry_run_real(uint64_t n, uint32_t workers, uint32_t batch, int prec,
+                            int direction, pifft_plan_info* info);
+int pifft_plan_is_real(const pifft_plan* plan);
 
 /* Diagnostics (no reference counterpart): the registry of compiled k_pass
  * instances, and which of them a plan would launch.  pifft_instance_desc
