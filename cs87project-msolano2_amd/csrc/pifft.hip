@@ -1,6 +1,6 @@
-// cs87project-msolano2_amd/csrc/pifft.hip -- libpifft.so: planner + C-ABI shim.
+// cs87project-msolano2_amd/csrc/pifft.hip -- libpifft.so: plan construction + C-ABI shim.
 //
-// Implements include/pifft.h.  The host side plans the reference's two stages
+// Implements include/pifft.h.  The host side plans (the policy: pifft_planner.h) the reference's two stages
 // (CPU.c:419-448 tree, CPU.c:463-478 cylinder) as a short list of kernel
 // launches (pifft_kernels.h) over device buffers:
 //
@@ -19,6 +19,7 @@
 #endif
 #include "pifft_gather.h"
 #include "pifft_kernels.h"
+#include "pifft_planner.h"
 #include "pifft_real.h"
 #include "pifft_table.h"
 #include "../../include/pifft.h"
@@ -27,7 +28,6 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,37 +44,11 @@ using namespace pifft;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return -1;
-}
-
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-
-// Planner tuning variables (PIFFT_* below) are read only when PIFFT_TUNING=1
-// is set: a variable inherited from a shell never changes the product's plan
-// (tests/test_planner.py::test_stray_tuning_variables_are_ignored).  Each
-// default is the measured winner cited where it is read.
-bool tuning_on() {
-    const char* s = getenv("PIFFT_TUNING");
-    return s && s[0] == '1' && s[1] == 0;
-}
-int env_int(const char* name, int dflt) {
-    if (!tuning_on()) return dflt;
-    const char* s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
 
 // Test-only fault injection for the multi-GPU error paths, which a one-GPU
 // box cannot otherwise reach (tests/test_gpu_parity.py): PIFFT_FAULT=<site>
@@ -106,18 +80,12 @@ bool fault_at(const char* site) {
 // bound stop event otherwise made C3's 44-us kernel read 50 us)
 constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
 
-bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
 // 1-D grid for a grid-stride kernel of `total` items at 256 threads/block:
 // capped so the launch's work-item count stays far below 2^32
 unsigned stride_grid(uint64_t total) {
     const uint64_t blocks = (total + 255) / 256;
     return (unsigned)(blocks < 262144 ? (blocks ? blocks : 1) : 262144);
-}
-int ilog2u(uint64_t x) {
-    int l = 0;
-    while (x > 1) { x >>= 1; l++; }
-    return l;
 }
 uint32_t bitrev(uint32_t x, int m) { return m ? (__builtin_bitreverse32(x) >> (32 - m)) : 0u; }
 
@@ -170,7 +138,10 @@ std::atomic<unsigned char>* found_log() {
     return f;
 }
 
-const PassKernel* find_pass(int prec, int R, int C, int mode, int nts = 0, int lp = 0, int vpt = 16) {
+}  // namespace
+
+// the planner's registry lookup (pifft_planner.h)
+const PassKernel* pifft::find_pass(int prec, int R, int C, int mode, int nts, int lp, int vpt) {
     const auto& all = pass_kernels();
     for (size_t i = 0; i < all.size(); i++) {
         const PassKernel& k = all[i];
@@ -181,6 +152,8 @@ const PassKernel* find_pass(int prec, int R, int C, int mode, int nts = 0, int l
     }
     return nullptr;
 }
+
+namespace {
 
 // The swapping twins of the instances (inverse plans), a table of their own:
 // the registry above, pifft_instance_* and the committed instance lists know
@@ -214,9 +187,7 @@ const TwinKernel* find_twin(const PassKernel& k, int sw) {
 // the twins of the tree and interleave kernels: (forward kernel, sw) -> twin
 const void* find_aux_twin(const void* fn, int sw) {
     struct Aux {
-        const void* fwd;
-        int sw;
-        const void* twin;
+        const void *fwd; int sw; const void *twin;
     };
 #define PIFFT_TREE_TWINS(T, L)                                                                    \
     {(const void*)&k_tree<T, L>, 1, (const void*)&k_tree_sw<T, L, 1>},                            \
@@ -244,6 +215,14 @@ enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, ST
 // BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real)
 enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, NBUF = 5 };
 
+// a step's twiddle tables as byte offsets into the plan's blob (kNoTable:
+// none); materialise resolves them into pa / ta / ra once, launch_step never
+constexpr size_t kNoTable = (size_t)-1;
+struct StepTables {
+    size_t r = kNoTable, lo = kNoTable, hi = kNoTable;  // a pass's w_R and two-level w_M; a real step's two-level w_N
+    size_t tree_direct = kNoTable, tree_lo = kNoTable, tree_hi = kNoTable;  // TreeTw
+};
+
 struct Step {
     int kind = 0;
     const void* fn = nullptr;
@@ -258,30 +237,23 @@ struct Step {
     uint64_t il_total = 0;
     uint32_t il_log_n = 0, il_log_p = 0;
     RealArgs ra{};  // STEP_R2C_POST / STEP_C2R_PRE
+    StepTables tab;
     uint64_t bytes = 0;
 };
 
 }  // namespace
 
-struct pifft_plan {
-    uint64_t n = 0, m = 0;
-    uint32_t P = 1, q0 = 0, nq = 1, batch = 1;
-    int prec = 64, device = 0, flags = 0;
-    int lp = 0, log_n = 0, log_m = 0;
-    size_t esz = 16;
-    bool natural = true;
-    bool bitrev = false;  // PIFFT_OUT_BITREV
+struct pifft_plan : pifft::PlanShape {  // (the shape it was planned for, pifft_planner.h)
+    int device = 0, flags = 0;
     bool ilv = false;     // the last pass stores natural order itself (PassArgs::ilv_log)
     bool wil = false;     // worker-interleaved layout (PassArgs::wil, MODE | 8 passes)
-    bool separate_tree = false;  // PIFFT_SEPARATE_TREE: never fuse the tree into a pass
     bool inverse = false;        // PIFFT_INVERSE: the first / last launch swap re/im (make_inverse)
     // pifft_plan_create_real: 0 complex, 1 R2C, 2 C2R.  Every field above and
     // below describes the inner N/2-point complex plan (n = real_n / 2)
     int real = 0;
     uint64_t real_n = 0;
     size_t bytes_z = 0;
-    void* d_rtw = nullptr;  // the fix-up step's two-level w_N table
-    size_t rtw_bytes = 0;
+    size_t rtw_bytes = 0;  // the fix-up step's two-level w_N table (in the blob, after the inner plan's tw_bytes)
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -398,7 +370,7 @@ struct TableBuilder {
 };
 
 struct TwoLevel {
-    size_t lo = 0, hi = 0;
+    size_t lo = kNoTable, hi = kNoTable;
     uint32_t h = 0;
 };
 
@@ -427,284 +399,12 @@ uint64_t interleave_threads(uint64_t total, int lp, int prec, uint64_t n) {
     return interleave_tiled(prec, lp, n) ? (total / IL_TILE) * 256 : total;
 }
 
-struct PassChoice {
-    int R, C, mode, nts;
-    int vpt = 16;
-};
-
-// Tile = R x C elements per workgroup (C adjacent lines of an R-point sub-FFT).
-// Default tile 8192 (fp64) / 16384 (fp32): 128 KiB of data in registers, one
-// component (64 KiB) in LDS at a time -> two workgroups per CU; at R = 512 the
-// lines give 256-B contiguous row segments (the HBM-efficient width measured
-// by tools/probe_bw.hip).
-int tile_elems(int prec) {
-    return env_int(prec == 64 ? "PIFFT_TILE64" : "PIFFT_TILE32", 8192);
-}
-
-int pick_lines(int prec, int R, uint64_t ntrans_lines_cap, uint64_t total_lines, const char* env_c, int mode,
-               int strided_tile = 0) {
-    int C = env_int(env_c, 0);
-    // single pass: lines are whole contiguous transforms, no segment-width
-    // constraint -> small tiles (measured best: C = 4096/R, i.e. C=1 at 4096)
-    int tile = mode == 0   ? env_int(prec == 64 ? "PIFFT_SINGLE_TILE64" : "PIFFT_SINGLE_TILE32", 4096)
-               : mode == 1 ? env_int(prec == 64 ? "PIFFT_FIRST_TILE64" : "PIFFT_FIRST_TILE32", tile_elems(prec))
-                           : tile_elems(prec);
-    if (strided_tile && (mode == 1 || mode == 2)) tile = strided_tile;  // (the packed VPT-32 fp32 tile)
-    // fp64 strided passes of R <= 256, not the fused tree pass (mode 3): a
-    // 4096-value tile.  At 8192 (R = 256, C = 32, 512 threads) the kernel
-    // spills 20 B/lane at its 128-VGPR budget; at C = 16 it runs 256 threads
-    // at 138 VGPRs, 3 workgroups per CU.  Measured on MI355X
-    // (profiles/r02_smallr_tile.log): 2^22 -7 %, 2^23 -12 %, 2^24 -4 %, the
-    // 2^28 worker of 8 -1.5 %; the fused pass itself loses at C = 16 (156
-    // VGPRs), so it keeps the 8192 tile
-    if (prec == 64 && (mode == 1 || mode == 2) && R <= 256) tile = env_int("PIFFT_SMALLR_TILE64", 4096);
-    if (mode == 3) mode = 1;  // the fused first pass: the first-pass tile, mode-1 line rules
-    if (C <= 0) C = tile / R;
-    if (C < 1) C = 1;
-    if (C > 64) C = 64;
-    if (R <= 8) C = 64;
-    while (C > 1 && (uint64_t)C > ntrans_lines_cap && R > 8) C /= 2;
-    // fill the chip: at least ~2 workgroups per CU (small transforms)
-    const uint64_t min_wg = (uint64_t)env_int("PIFFT_MIN_WORKGROUPS", 512);
-    // strided passes are instantiated for C >= 4 (and fp64 C = 2 at R = 512-2048, PIFFT_STRIDED_CMIN=2)
-    const int cmin = mode == 0 ? 1 : env_int("PIFFT_STRIDED_CMIN", 4);
-    while (C > cmin && R > 8 && total_lines / (uint64_t)C < min_wg) C /= 2;
-    while (C > cmin && !find_pass(prec, R, C, mode)) C /= 2;
-    return C;
-}
-
-// non-temporal streaming when a pass moves more than the Infinity Cache holds,
-// and for 16-64 MiB passes (measured on MI355X, profiles/r02_nt_sweep.log:
-// fp64 2^20 P=1 26 -> 24 us, P=8 44 -> 41 us, fp32 4096 x 1024 16 -> 13 us,
-// the 2^21-point worker of 8 95 -> 84 us; but 8-16 MiB and 128-256 MiB passes
-// lose 5-40 %)
-int pick_nts(uint64_t pass_bytes) {
-    const int force = env_int("PIFFT_NT", -1);
-    if (force >= 0) return force ? 1 : 0;
-    return (pass_bytes > (256ull << 20) || (pass_bytes > (16ull << 20) && pass_bytes <= (64ull << 20))) ? 1 : 0;
-}
-
-// HBM rate of a pass side, by the contiguous bytes per row segment (TB/s).
-// Measured on MI355X with tools/probe_bw.hip (strided tile copies) and the
-// pass kernels themselves (profiles/r01_tune_*.log); contiguous ~5.6.
-double seg_rate(double seg_bytes) {
-    if (seg_bytes >= 1024) return 5.6;
-    if (seg_bytes >= 512) return 5.5;
-    if (seg_bytes >= 256) return 5.3;
-    if (seg_bytes >= 128) return 4.2;
-    if (seg_bytes >= 64) return 2.6;
-    return 1.5;
-}
-
-// Whole-pass HBM rate (TB/s, both sides) by the pass's position in a plan and
-// its strided row-segment width, for HBM-bound plans without a fused tree
-// (round 3).  Measured on MI355X (profiles/r03_fp64_radix_order.log,
-// r03_fp32_radix_order.log; fp64 2^28 / 2^29, fp32 packed 2^28): a 256-B pass
-// runs 5.9 / 5.6 / 5.25 TB/s first / in the middle / last, a 128-B one 5.0 /
-// 4.8 / 4.8 -- the last pass's strided stores into the caller's unpadded
-// output are slow at either width, so the narrow pass costs least there.
-// fp64 2^28: 512-512-1024 4.72 ms vs 1024-512-512 4.82 (same box); fp32 2^28
-// 2.47 vs 2.60 ms; fp64 2^29 9.41 vs 9.65 ms.  Same for both precisions.
-double pass_rate(double seg_bytes, bool first, bool last) {
-    if (seg_bytes >= 256) return first ? 5.9 : last ? 5.25 : 5.6;
-    if (seg_bytes >= 128) return first ? 5.0 : 4.8;
-    return seg_rate(seg_bytes);
-}
-
-// Local FFT of length M as passes.  A single LDS/register-resident pass when M
-// fits (M <= 2^14); otherwise k Stockham passes with balanced radices, k and
-// the radix order chosen by a bandwidth model: each pass moves its bytes at
-// the rate of its narrowest strided side (C*esz-byte row segments).
-// heavy_first: the first pass also evaluates the tree (reads P leaves per
-// input, P = 2^lp), so its read side dominates.
-// fp32 strided passes at 32 values per thread, packed (k_pass VPT 32): a
-// 16384-value tile on 512 threads, two workgroups per CU -- the bytes and
-// row-segment widths of the fp64 8192-value tile, so fp32 2^28 runs in three
-// passes (1024-512-512 at C = 16/32/32) instead of four 128-point ones.
-// Measured on MI355X (profiles/r03_fp32_packed_vpt32.log): fp32 2^28 3.36 ->
-// 2.67 ms, 2^30 13.7 -> 11.6 ms; 2^26 (512 MiB per side) 0.63 -> 0.65 ms.
-// The rule: data beyond 1 GiB per side, no fused tree pass (no packed MODE 3
-// instances).  PIFFT_VPT32: -1 this rule, 0 never, 1 whenever instantiated.
-bool use_vpt32(int prec, uint64_t M, uint64_t ntrans, int heavy_lp) {
-    const int force = env_int("PIFFT_VPT32", -1);
-    if (prec != 32 || heavy_lp || force == 0) return false;
-    return force == 1 || ntrans * M * 8 >= (1ull << 30);
-}
-
-// pos_ok: the position-aware pass rates may price this plan (not for the
-// worker-interleaved layout, whose passes move rows of all workers: there the
-// narrow pass last measured 1-14 % slower, profiles/r03_pos_model_shapes.log)
-// single_max: the longest one-pass local FFT (log2; default 14, PIFFT_SINGLE_MAX_LOG)
-int plan_passes(uint64_t M, int prec, uint64_t ntrans, std::vector<PassChoice>& out, int heavy_lp = 0,
-                bool allow_v32 = true, bool pos_ok = true, int single_max = -1) {
-    out.clear();
-    if (M <= 1) return 0;
-    const int logm = ilog2u(M);
-    const size_t esz = prec == 64 ? 16 : 8;
-    if (single_max < 0) single_max = env_int("PIFFT_SINGLE_MAX_LOG", 14);
-    const bool v32 = allow_v32 && M > (1ull << single_max) && use_vpt32(prec, M, ntrans, heavy_lp);
-    const int stile = v32 ? 16384 : 0;
-    const int nts = pick_nts(2 * ntrans * M * esz);
-    if (logm <= single_max) {
-        const int R = (int)M;
-        const int C = pick_lines(prec, R, ntrans, ntrans, prec == 64 ? "PIFFT_SINGLE_C64" : "PIFFT_SINGLE_C32", 0);
-        if (!find_pass(prec, R, C, 0, nts)) return fail("no pass kernel for R=%d C=%d", R, C);
-        // tuning: 8 values per thread (radix-8 stages, twice the waves per
-        // sub-FFT) -- measured slower than 16 at every batch size
-        // (profiles/r02_vpt_sweep.log), so only on request and if instantiated
-        const int vpt = env_int("PIFFT_SINGLE_VPT", 16);
-        if (vpt != 16 && find_pass(prec, R, C, 0, nts, 0, vpt)) {
-            out.push_back({R, C, 0, nts, vpt});
-            return 0;
-        }
-        out.push_back({R, C, 0, nts});
-        return 0;
-    }
-    // tuning: explicit log2 radices, e.g. PIFFT_RADIX_LOGS=10,10,8 (must sum to log2 M)
-    bool explicit_radices = false;
-    if (const char* rl = tuning_on() ? getenv("PIFFT_RADIX_LOGS") : nullptr) {
-        std::vector<int> logs;
-        for (const char* c = rl; *c;) {
-            char* end = nullptr;
-            const long v = strtol(c, &end, 10);
-            if (end == c) break;
-            logs.push_back((int)v);
-            c = *end ? end + 1 : end;
-        }
-        int sum = 0;
-        for (int l : logs) sum += l;
-        if (sum == logm && logs.size() > 1) {
-            for (size_t p = 0; p < logs.size(); p++) {
-                const int R = 1 << logs[p], mode = p == 0 ? 1 : 2;
-                const int C = pick_lines(prec, R, M >> logs[p], ntrans * (M >> logs[p]),
-                                         prec == 64 ? "PIFFT_COL_C64" : "PIFFT_COL_C32",
-                                         (p == 0 && heavy_lp) ? 3 : mode, stile);
-                if (!find_pass(prec, R, C, mode, nts)) return fail("no pass kernel R=%d C=%d", R, C);
-                out.push_back({R, C, mode, nts});
-            }
-            explicit_radices = true;
-        }
-    }
-    const int rmax_log = env_int(prec == 64 ? "PIFFT_COL_RMAX_LOG64" : "PIFFT_COL_RMAX_LOG32", 10);
-    const int kmin = (logm + rmax_log - 1) / rmax_log;
-    const int kmax = env_int("PIFFT_PASSES", 0) > 0 ? env_int("PIFFT_PASSES", 0) : kmin + 1;
-    double best = 1e300;
-    // data that stays in the 256 MiB Infinity Cache is not bound by HBM row
-    // segments: fewest passes there
-    const bool resident = 2 * ntrans * M * esz <= (256ull << 20);
-    const int klast = resident && env_int("PIFFT_PASSES", 0) <= 0 ? kmin : kmax;
-    for (int k = env_int("PIFFT_PASSES", 0) > 0 ? kmax : kmin; k <= klast && !explicit_radices; k++) {
-        if (logm < 4 * k) break;  // every radix >= 16
-        const int base = logm / k, extra = logm % k;
-        const int force_order = env_int("PIFFT_ORDER", -1);  // tuning: 0 or 1 only
-        for (int order = 0; order < 2; order++) {  // 0: larger radices first, 1: smaller first
-            if (force_order >= 0 && order != force_order) continue;
-            // a fused tree+first pass runs best with the larger radix (R = 512,
-            // C = 16) first: measured 1-3 % over the model's pick at P = 4, 8.
-            // Not when that radix leaves the P-fold leaf reads narrower than
-            // 256-B segments (R = 1024, C = 8 at fp64): then the model picks
-            // between both orders (config 5, 2^29 per worker: 512-1024-1024
-            // 19.7 ms vs 256-128-128-128 21.3 ms, profiles/r01_tune_c5.log).
-            // fp64 only: the fp32 tile gives R = 1024 128-B segments too, but
-            // the other order there loses the fused kernel (no instance)
-            if (force_order < 0 && heavy_lp > 0 && order == 1) {
-                const int R0 = 1 << (base + (extra > 0 ? 1 : 0));
-                const int C0 = pick_lines(prec, R0, M >> ilog2u((uint64_t)R0), ntrans * (M >> ilog2u((uint64_t)R0)),
-                                          prec == 64 ? "PIFFT_COL_C64" : "PIFFT_COL_C32", 3);
-                if (prec != 64 || (size_t)C0 * esz >= 256) continue;  // fp32: measured cases only
-            }
-            std::vector<PassChoice> cand;
-            double cost = 0.0;
-            bool ok = true;
-            // the position rates were measured on passes of >= 128-B segments:
-            // a candidate with a narrower pass keeps the segment-width model
-            bool pos = pos_ok && !resident && !heavy_lp && env_int("PIFFT_POS_MODEL", 1);
-            for (int p = 0; p < k && pos; p++) {
-                const int bits = order ? base + (p >= k - extra ? 1 : 0) : base + (p < extra ? 1 : 0);
-                const int C = pick_lines(prec, 1 << bits, M >> bits, ntrans * (M >> bits),
-                                         prec == 64 ? "PIFFT_COL_C64" : "PIFFT_COL_C32", p == 0 ? 1 : 2, stile);
-                pos = (size_t)C * esz >= 128;
-            }
-            for (int p = 0; p < k && ok; p++) {
-                const int bits = order ? base + (p >= k - extra ? 1 : 0) : base + (p < extra ? 1 : 0);
-                const int R = 1 << bits;
-                const int mode = p == 0 ? 1 : 2;
-                const int C = pick_lines(prec, R, M >> bits, ntrans * (M >> bits),
-                                         prec == 64 ? "PIFFT_COL_C64" : "PIFFT_COL_C32",
-                                         (p == 0 && heavy_lp) ? 3 : mode, stile);
-                if (!find_pass(prec, R, C, mode, nts)) { ok = false; break; }
-                const double rs = seg_rate((double)C * esz);           // strided side
-                const double side = (double)ntrans * M * esz * 1e-12;  // TB per side
-                const double reads = (p == 0 && heavy_lp) ? side * (1 << heavy_lp) : side;
-                if (pos)
-                    cost += 2 * side / pass_rate((double)C * esz, p == 0, p == k - 1);
-                else
-                    cost += reads / rs + side / (mode == 1 ? 5.6 : rs);
-                cand.push_back({R, C, mode, nts});
-            }
-            if (ok && cost < best) {
-                best = cost;
-                out = cand;
-            }
-        }
-    }
-    if (out.empty()) return fail("no pass decomposition for M=2^%d", logm);
-    // the packed VPT-32 passes for the 16384-value tile (every strided pass
-    // must have its instance, else the plan is redone at the 8192 tile)
-    if (v32) {
-        for (auto& pc : out) {
-            if (pc.mode != 1 && pc.mode != 2) continue;
-            if (!find_pass(prec, pc.R, pc.C, pc.mode, pc.nts, 0, 32))
-                return plan_passes(M, prec, ntrans, out, heavy_lp, false, pos_ok);
-            pc.vpt = 32;
-        }
-    }
-    // The fused tree pass of a small one-worker slice at 8 values per thread
-    // (radix-8 stages, twice the waves per workgroup) when it has R <= 512
-    // points and at most 128 workgroups: a latency-bound launch on a fraction
-    // of the CUs, whose P leaf loads and tree per value then spread over twice
-    // the threads.  Measured on MI355X (profiles/r04d_fused_vpt8.log): fp64
-    // local 2^15-2^18 +4.5-31 % (config 2's slice 14.05 -> 12.66 us), fp32
-    // +0.6-4 %; R = 1024 -2-3 %, 256 workgroups ties.  PIFFT_FUSED_VPT: the
-    // values per thread instead (tuning).
-    if (heavy_lp && !out.empty() && out[0].mode == 1) {
-        PassChoice& pc = out[0];
-        const uint64_t wgs = (ntrans * (M / (uint64_t)pc.R) + pc.C - 1) / (uint64_t)pc.C;
-        const int fvpt = env_int("PIFFT_FUSED_VPT", (pc.R <= 512 && wgs <= 128) ? 8 : 16);
-        if (fvpt != pc.vpt && find_pass(prec, pc.R, pc.C, 3, pc.nts, heavy_lp, fvpt)) pc.vpt = fvpt;
-    }
-    // The last strided pass of a small fp64 plan (R <= 512, <= 256
-    // workgroups) at 8 values per thread too: measured on MI355X
-    // (profiles/r04k_slice.log, r04k_shapes.log) config 2's one-GPU slice
-    // 12.7 -> 12.2 us (+3.8 %), fp64 slices of local 2^16-2^19 +1.6-5 %, P = 1
-    // 2^16-2^18 +5-6 %; 4 values per thread +2.6 % (slice).  PIFFT_LAST_VPT:
-    // the values per thread instead (tuning, below).
-    if (prec == 64 && out.size() > 1 && out.back().mode == 2 && out.back().vpt == 16) {
-        PassChoice& pc = out.back();
-        const uint64_t wgs = (ntrans * (M / (uint64_t)pc.R) + pc.C - 1) / (uint64_t)pc.C;
-        if (pc.R <= 512 && wgs <= 256 && find_pass(prec, pc.R, pc.C, 2, pc.nts, 0, 8)) pc.vpt = 8;
-    }
-    // tuning: lines per workgroup (its write side's segment width) and values
-    // per thread of the last pass
-    const int last_c = env_int("PIFFT_LAST_C", 0), last_vpt = env_int("PIFFT_LAST_VPT", 0);
-    if ((last_c > 0 || last_vpt > 0) && out.size() > 1) {
-        PassChoice& b = out.back();
-        const int c = last_c > 0 ? last_c : b.C, v = last_vpt > 0 ? last_vpt : b.vpt;
-        if (find_pass(prec, b.R, c, b.mode, b.nts, 0, v)) {
-            b.C = c;
-            b.vpt = v;
-        }
-    }
-    return 0;
-}
-
 void release(pifft_plan* p) {
     if (!p) return;
     DeviceGuard g(p->device);
     for (int b = BUF_W; b < NBUF; b++)
         if (p->buf[b]) (void)hipFree(p->buf[b]);
     if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_rtw) (void)hipFree(p->d_rtw);
     if (p->d_hin) (void)hipFree(p->d_hin);
     if (p->d_hout) (void)hipFree(p->d_hout);
     if (p->d_gather) (void)hipFree(p->d_gather);
@@ -720,325 +420,68 @@ void release(pifft_plan* p) {
     delete p;
 }
 
-struct Elem {
-    std::vector<Step> steps;
+
+// Step 2 of a plan, the table layout: where each twiddle table choose_plan's
+// choice needs sits in the plan's one blob (offsets only; the builder fills
+// in the values unless it is size_only).
+struct TableLayout {
+    size_t tree_direct = kNoTable;  // the reference-formula tree table
+    TwoLevel tree2;                 // two-level w_N (the tree)
+    std::vector<size_t> tw_r;       // per pass: w_R
+    TwoLevel pass2;                 // two-level w_M (plans of >= 2 passes)
 };
 
-// dry: plan only (pifft_plan_dry_run) -- no device, no allocation
-int build_plan(pifft_plan* p, bool dry = false) {
+TableLayout layout_tables(const PlanShape& s, const PlanChoice& ch, TableBuilder& tb) {
+    TableLayout tl;
+    // --- tree tables (w_N) ---
+    if (ch.tree_tw == TREE_TW_DIRECT || ch.tree_tw == TREE_TW_WIL_FACTORED)
+        tl.tree_direct = tb.reference_omega_levels(s.n, s.lp);
+    if (ch.tree_tw == TREE_TW_FACTORED || ch.tree_tw == TREE_TW_WIL_FACTORED) tl.tree2 = two_level(tb, s.n);
+    // --- pass tables ---
+    tl.tw_r.resize(ch.passes.size());
+    for (size_t i = 0; i < ch.passes.size(); i++) {
+        size_t found = kNoTable;
+        for (size_t j = 0; j < i; j++)
+            if (ch.passes[j]->R == ch.passes[i]->R) found = tl.tw_r[j];
+        tl.tw_r[i] = (found != kNoTable) ? found : tb.roots(ch.passes[i]->R, ch.passes[i]->R, 1);
+    }
+    if (ch.passes.size() > 1) tl.pass2 = two_level(tb, s.m);  // (every worker-interleaved plan has >= 2 passes)
+    tb.align();
+    return tl;
+}
+
+// Step 3, the launches: [tree] [passes] [interleave] over the ping-pong
+// buffers, every argument but the device pointers (tables are offsets into
+// the blob, Step::tab).  A dry run ends here.
+int assemble_steps(pifft_plan* p, const PlanChoice& ch, const TableLayout& tl) {
     const size_t esz = p->esz;
     const uint64_t ntrans = (uint64_t)p->batch * p->nq;  // local transforms
-    std::vector<PassChoice> passes;
-    // One worker per plan: the tree is fused into the first pass, which reads
-    // the input once.  (Several workers per plan re-reading all P leaves in
-    // each worker's fused pass measured no consistent win, profiles/
-    // r02_fuse_all.log; removed in round 4.)
-    // All P <= 16 workers of a natural-order plan on this GPU, with a
-    // multi-pass local FFT: the worker-interleaved layout (PassArgs::wil).
-    // The tree's one launch writes z_q[i] at i P + q, every pass reads and
-    // writes rows holding all workers' values side by side, and the last pass
-    // stores worker q at slot bitrev(q) -- the natural-order result, without
-    // an interleave launch or scattered 16-B stores.  PIFFT_WORKER_IL=0: the
-    // slice-major layout (+ interleave launch or natural-order store).
-    const bool wil_ok = p->natural && p->P > 1 && p->nq == p->P && p->lp <= 4 && env_int("PIFFT_WORKER_IL", 1);
-    const bool may_fuse = p->P > 1 && p->nq == 1 && p->lp <= 4 && !p->separate_tree && env_int("PIFFT_FUSE_TREE", 1);
-    if (plan_passes(p->m, p->prec, ntrans, passes, may_fuse ? p->lp : 0, true, !wil_ok)) return -1;
-    // the same radices, every pass a worker-interleaved MODE 2 (| 8) pass at
-    // the C of a MODE 2 pass whose lines run over all workers
-    auto to_wil = [&](std::vector<PassChoice>& w) -> bool {
-        bool ok = true;
-        for (auto& pc : w) {
-            const uint64_t lines = p->m / (uint64_t)pc.R;
-            pc.C = pick_lines(p->prec, pc.R, lines << p->lp, ntrans * lines,
-                              p->prec == 64 ? "PIFFT_COL_C64" : "PIFFT_COL_C32", 2);
-            pc.mode = 2 | 8;
-            pc.vpt = 16;
-            // tuning: at least this many lines per workgroup (e.g. P, so a
-            // row holds every worker's value), if instantiated
-            // (default P: 8 workers at C = 8 instead of 4 -- C2 35 -> 32 us,
-            // fp32 2^20 P = 8 25 -> 24 us, 2^28 P = 8 unchanged at C = 16;
-            // profiles/r03_worker_interleaved.log)
-            const int cmin = env_int("PIFFT_WIL_CMIN", (int)p->P);
-            if (cmin > pc.C && find_pass(p->prec, pc.R, cmin, pc.mode, pc.nts)) pc.C = cmin;
-            ok = ok && find_pass(p->prec, pc.R, pc.C, pc.mode, pc.nts) != nullptr;
-            // config-2-sized plans (<= 32 MiB of data): 8 values per thread
-            // where instantiated (config 2 29.9 -> 29.0 us, profiles/
-            // r04d_wil_vpt8_c2.log); PIFFT_WIL_VPT: instead (tuning)
-            const bool small = (uint64_t)p->batch * p->n * esz <= (32ull << 20);
-            const int wvpt = env_int("PIFFT_WIL_VPT", small ? 8 : 16);
-            if (wvpt != pc.vpt && find_pass(p->prec, pc.R, pc.C, pc.mode, pc.nts, 0, wvpt)) pc.vpt = wvpt;
-        }
-        return ok;
-    };
-    if (wil_ok && passes.size() > 1) {
-        std::vector<PassChoice> w = passes;
-        if (to_wil(w)) {
-            passes = w;
-            p->wil = true;
-        }
-    }
-    // A single transform whose local FFT is one pass (M <= 2^14) would run
-    // tree + pass + interleave launches.  From M = 2^11 up the
-    // worker-interleaved plan with every worker's tree fused into its first
-    // pass (MODE 11 below: the first radix, then an M / R1-point pass) does
-    // it in two, kept only where that fused plan exists (round 5,
-    // profiles/r05w_small_wil.log: fp64 2^15 P = 2 22 -> 13 us, 2^16 P = 4
-    // 23 -> 11, 2^17 P = 8 25 -> 12; fp32 2^17 P = 8 21 -> 9, 2^18 P = 16
-    // 25 -> 13; 9-30 % at the other sizes).  PIFFT_WIL_SINGLE=0: off.
-    // And a transform that fits one tile (P M <= 8192 values, from 1024: the
-    // reference's own GPU sweep, cuda/run-experiments:16) runs every worker's
-    // tree and its whole M-point FFT in ONE launch: the fused pass at J = 1 (C
-    // = P lines of R = M points) storing natural order (PIFFT_WIL_ONE_LAUNCH=0:
-    // off).  Batched, one workgroup per transform: 1.2-2.8x faster than tree +
-    // pass (profiles/r05bo_batched_one_launch_ab.log; PIFFT_WIL_ONE_BATCH=0: off);
-    // and batched two-pass plans 11-40 % (r05bt_batched_two_pass_ab.log;
-    // PIFFT_WIL_SINGLE_BATCH=0: off).
-    // The two-pass plan from M = 2^11 (fp64 2^14 P = 8 11 -> 10 us, fp32 8 vs
-    // 11, fp32 2^15 P = 16 12 vs 14: profiles/r05za_small_plan_edges.log).
-    // (PIFFT_WIL_ONE_MAX: the largest one-launch transform, values -- 16384
-    // measured slower; the instances exist only where they compile spill-free.
-    // PIFFT_WIL_SINGLE_MIN_LOG: the two-pass plan's smallest M, log2.  Tuning.)
-    const uint64_t pm = (uint64_t)p->P * p->m;
-    int nts0 = pick_nts(2 * ntrans * p->m * esz);
-    // (fp64 P = 2 at M = 4096 spills at 16 values per thread: 8, 1024 threads,
-    // batched only -- 64 transforms 21 -> 13 us, one 10 -> 12: profiles/r05v8_*)
-    const int vpt0 = find_pass(p->prec, (int)p->m, (int)p->P, 11, 0, p->lp) ? 16 : p->batch >= 64 ? 8 : 0;
-    if (nts0 && !find_pass(p->prec, (int)p->m, (int)p->P, 11, nts0, p->lp, vpt0)) nts0 = 0;  // (nt forms not instantiated)
-    // (P = 32 too, one launch only: two threads per position, each evaluating
-    // the tree pruned to half the workers)
-    const bool wil_ok5 = p->natural && p->P > 1 && p->nq == p->P && p->lp == 5 && env_int("PIFFT_WORKER_IL", 1);
-    const bool one_ok = (wil_ok || wil_ok5) && passes.size() == 1 && pm >= 1024 &&
-                        pm <= (uint64_t)env_int("PIFFT_WIL_ONE_MAX", 8192) && env_int("PIFFT_WIL_ONE_LAUNCH", 1) &&
-                        find_pass(p->prec, (int)p->m, (int)p->P, 11, nts0, p->lp, vpt0);
-    const bool wil_single = (wil_ok || one_ok) && passes.size() == 1 && env_int("PIFFT_WIL_SINGLE", 1) &&
-                            (((p->batch == 1 || env_int("PIFFT_WIL_SINGLE_BATCH", 1)) &&
-                              p->m >= (1ull << env_int("PIFFT_WIL_SINGLE_MIN_LOG", 11))) ||
-                             (one_ok && (p->batch == 1 || env_int("PIFFT_WIL_ONE_BATCH", 1))));
-    if (wil_single) p->wil = true;
-    // The worker-interleaved plan with its tree fused into the first pass
-    // (MODE 11, k_pass wil_tree_to_lds): a tile of J adjacent line indices x
-    // all P workers loads each position's P leaves once (J esz-byte leaf
-    // rows) and evaluates every worker's tree there, so the tree launch (N
-    // read + N written) and the first pass's re-read of its output are gone.
-    // The first radix is what that tile leaves (8192 / (J P)), the rest of
-    // the local FFT is planned as usual.  J by measurement (round 5,
-    // profiles/r05m_wil_fuse_j.log, the separate tree launch in brackets):
-    //   fp64, J = 8: config 2 (2^20 P = 8) 26 us (29), 2^20 P = 4 23 (31),
-    //     P = 2 25 (31), 2^24 P = 8 310 (381), 2^26 P = 4 1.18 ms (1.50),
-    //     2^28 P = 8 4.98 ms (6.31), P = 16 5.84 (6.13); but P = 16 below
-    //     256 MiB ties or loses (2^20: 28-45 vs 26 us) -> separate there;
-    //     J = 16 (256-B leaf rows, first radix 64 at P = 8) loses on the
-    //     remaining passes it leaves (a 1024 / 2048 pass at 8 lines);
-    //   fp32: J = 8 up to 32 MiB (2^20 P = 8 20 vs 24 us), J = 16 up to
-    //     1 GiB (2^24 P = 8 165 vs 208 us); 2^28 P = 8 keeps the separate tree
-    //     (3.26 vs 3.39-3.51 ms: its remaining passes at 8-B values get
-    //     128-B rows).
-    // Two refinements for P <= 8 (round 5, profiles/r05s_*, r05t_*, r05u_*;
-    // every output checked against the default plan's):
-    //   - where the 8192-value tile leaves fewer than 256 workgroups (<= 2^20
-    //     values: 128), the tile is halved and J = 4, so every CU gets one:
-    //     config 2 26 -> 23 us, fp64 2^20 P = 4 23 -> 21, P = 2 25 -> 23,
-    //     2^19 P = 8 21 -> 18, 2^18 P = 8 16 -> 14; fp32 2^20 P = 2-8 -1 us;
-    //   - where J = 8 leaves a remainder the rest of the plan splits in two
-    //     passes (> 2048 points) and J = 4 leaves one pass: J = 4 (fp64 2^22
-    //     P = 2 / 4 / 8: 68 / 65 / 64 -> 54 / 51 / 50 us); fp32 at P = 8 from a
-    //     2048-point remainder on (2^21 27 -> 24 us, 2^22 51 -> 42).  (fp32 at
-    //     P <= 4 keeps J = 8: its J = 4 remainder passes run at 4 lines, 32-B
-    //     rows: 2^22 P = 4 50 -> 75 us.)
-    // PIFFT_SEPARATE_TREE (CLI -u) or PIFFT_WIL_FUSE=0: the separate tree
-    // launch; PIFFT_WIL_FUSE_J: J (then the tile stays 8192 unless
-    // PIFFT_WIL_FUSE_TILE says otherwise), PIFFT_WIL_FUSE_TILE: the tile
-    // (values), PIFFT_WIL_FUSE_VPT: values per thread (tuning, tests).
-    uint32_t wil_fused_c = 0;
-    if (wil_single && one_ok && !p->separate_tree && env_int("PIFFT_WIL_FUSE", 1)) {
-        passes = {PassChoice{(int)p->m, (int)p->P, 11, nts0, vpt0}};
-        wil_fused_c = p->P;
-    }
-    if (p->wil && !wil_fused_c && !p->separate_tree && env_int("PIFFT_WIL_FUSE", 1)) {
-        const uint64_t data = (uint64_t)p->batch * p->n * esz;
-        const int jdef = p->prec == 64 ? ((p->lp <= 3 || data >= (256ull << 20)) ? 8 : 0)
-                                       : (data <= (32ull << 20) ? 8 : data <= (1ull << 30) ? 16 : 0);
-        int J = jdef, tile1 = tile_elems(p->prec);
-        if (jdef == 8 && p->lp <= 3) {
-            const uint64_t rest8 = p->m / (uint64_t)(tile1 / (8 << p->lp)), rest4 = rest8 / 2;
-            if ((uint64_t)p->batch * p->n / (uint64_t)tile1 < 256) {
-                tile1 /= 2;
-                J = 4;
-            } else if (rest8 > (p->prec == 64 ? 2048u : 1024u) && rest4 <= 2048 && (p->prec == 64 || p->lp == 3)) {
-                J = 4;
-            }
-        } else if (jdef == 8 && p->lp == 4) {
-            // fp32 P = 16: J = 4 where it leaves a remainder of at most 1024
-            // points (2^21: 41 -> 26 us; at 2048 its 4-line pass loses, 2^22
-            // 52 -> 90, r05u_wil_fuse_remainder.log)
-            const uint64_t rest8 = p->m / (uint64_t)(tile1 / (8 << p->lp));
-            if (rest8 > 1024 && rest8 / 2 <= 1024) J = 4;
-        } else if (jdef == 0 && p->lp == 4 && p->prec == 64 && data >= (32ull << 20) && data <= (64ull << 20)) {
-            J = 2;  // fp64 P = 16 at 32-64 MiB: fused at J = 2 (2^21 43 -> 37 us, 2^22 70 -> 65; 2^23 loses)
-        }
-        const int jenv = env_int("PIFFT_WIL_FUSE_J", -1);
-        if (jenv >= 0) {
-            J = jenv;
-            tile1 = tile_elems(p->prec);
-        }
-        tile1 = env_int("PIFFT_WIL_FUSE_TILE", tile1);
-        const int C1 = J > 0 ? J << p->lp : 0;
-        const int R1 = C1 > 0 ? tile1 / C1 : 0;
-        const int vpt1 = env_int("PIFFT_WIL_FUSE_VPT", 16);
-        const int nts1 = pick_nts(2 * ntrans * p->m * esz);
-        std::vector<PassChoice> rest;
-        const uint64_t m2 = R1 > 0 ? p->m / (uint64_t)R1 : 0;
-        bool ok = R1 >= 16 && (uint64_t)R1 < p->m && m2 >= (uint64_t)J && find_pass(p->prec, R1, C1, 11, nts1, p->lp, vpt1) &&
-                  plan_passes(m2, p->prec, ntrans * (uint64_t)R1, rest, 0, false, false) == 0;
-        // (worker-interleaved passes exist up to R = 2048: a longer single
-        // remainder becomes two balanced passes)
-        if (ok && rest.size() == 1 && rest[0].R > 2048) {
-            const int l = ilog2u(m2);
-            rest = {PassChoice{1 << ((l + 1) / 2), 0, 2, rest[0].nts}, PassChoice{1 << (l / 2), 0, 2, rest[0].nts}};
-        }
-        if (ok && to_wil(rest)) {
-            passes.clear();
-            passes.push_back({R1, C1, 11, nts1, vpt1});
-            for (const auto& pc : rest) passes.push_back(pc);
-            wil_fused_c = (uint32_t)C1;
-        }
-    }
-    if (wil_single && !wil_fused_c) {
-        // no fused plan: the single pass -- except P = 16 at fp64 (no fused
-        // pass below 256 MiB, above), where the worker-interleaved two-pass
-        // plan after its tree launch still saves the interleave launch (2^16
-        // 16 -> 15 us, 2^17 21 -> 16, 2^18 30 -> 19; r05w_small_wil.log)
-        std::vector<PassChoice> w;
-        p->wil = p->lp == 4 && p->batch == 1 && p->m >= 4096 && plan_passes(p->m, p->prec, ntrans, w, 0, false, false, ilog2u(p->m) - 1) == 0 &&
-                 w.size() == 2 && to_wil(w);
-        if (p->wil) passes = w;
-    }
-    if (p->bitrev && !passes.empty()) {
-        // the last pass stores in bit-reversed order: its MODE | 4 twin, at
-        // the planned C or the widest instantiated one below it
-        PassChoice& l = passes.back();
-        const int bm = l.mode, cmin = bm == 0 ? 1 : 4;
-        if (l.vpt == 8 && !find_pass(p->prec, l.R, l.C, bm | 4, l.nts, 0, 8)) l.vpt = 16;  // (no VPT-8 twin)
-        int C = l.C;
-        while (C > cmin && !find_pass(p->prec, l.R, C, bm | 4, l.nts, 0, l.vpt)) C /= 2;
-        if (!find_pass(p->prec, l.R, C, bm | 4, l.nts, 0, l.vpt))
-            return fail("no bit-reversed pass kernel R=%d C=%d mode=%d", l.R, l.C, bm);
-        l.C = C;
-        l.mode = bm | 4;
-    }
-
-    // All P workers on this plan, natural order, and an output small enough to
-    // stay in L2 / the Infinity Cache: the last pass stores each worker's bins
-    // at their natural positions bitrev(q) + P k itself (plain stores; the P
-    // workers' tiles of a line block back to back on one XCD) instead of a
-    // slice-major store plus an interleave launch.  Measured on MI355X
-    // (profiles/r02_ilv_store.log, wall per transform): fp64 2^18-2^22 P=2-16
-    // 1-22 % faster, fp32 2^20 P=8 7 %, batched single-pass plans (4096 x
-    // 4096 fp32 P=4, 1024 x 2^12 fp64 P=4) 13-16 %; 2^23 fp64 and 2^22 fp32
-    // (32 MiB) single transforms up to 5 % slower, few tiles (2^16: 8) 12 %.
-    // PIFFT_ILV: -1 this rule, 0 never, 1 always (where it applies).
-    {
-        const int force = env_int("PIFFT_ILV", -1);
-        const bool ok = p->natural && p->P > 1 && p->nq == p->P && !passes.empty() && !p->wil;
-        bool on = ok && force == 1;
-        if (ok && force < 0) {
-            const PassChoice& l = passes.back();
-            const uint64_t tiles = (ntrans * (p->m / (uint64_t)l.R) + l.C - 1) / (uint64_t)l.C;
-            const uint64_t cap_mib = passes.size() == 1 ? (uint64_t)env_int("PIFFT_ILV_SINGLE_MAX_MIB", 128)
-                                     : p->prec == 64    ? (uint64_t)env_int("PIFFT_ILV_MAX_MIB64", 64)
-                                                        : (uint64_t)env_int("PIFFT_ILV_MAX_MIB32", 16);
-            on = tiles >= (uint64_t)env_int("PIFFT_ILV_MIN_TILES", 256) &&
-                 (uint64_t)p->batch * p->n * esz <= (cap_mib << 20);
-        }
-        p->ilv = on;
-    }
-    if (p->ilv) passes.back().nts = 0;
-    TableBuilder tb(esz);
-    tb.size_only = dry;
-    // --- tree tables (w_N) ---
+    const size_t npass = ch.passes.size();
     const bool need_tree = p->P > 1;
-    size_t tree_direct = 0;
-    TwoLevel tree2;
-    bool tree_is_direct = false;
-    // The worker-interleaved plan's one tree launch (k_tree_wil) feeds its
-    // passes only -- its output is never observed, and the plan's result
-    // matches the oracle within tolerance either way -- so from 2^21 values
-    // up it takes the factored two-level twiddles (one small-table lookup per
-    // level and thread) instead of the reference-formula table, whose
-    // N (1 - 1/P) entries it otherwise reads beside the data (C2: 1.44x its
-    // algorithmic bytes, profiles/r05b_traffic_n2^20_f64_b1_P8_q8.json).
-    // Measured on MI355X (profiles/r05g_wil_tree.log): fp64 2^21 P = 8
-    // 46 -> 42 us, 2^22 P = 16 80 -> 70 us; but config 2 itself (fp64 2^20,
-    // P = 8: 512 workgroups, one round, latency-bound) 29 -> 31 us -- there
-    // the extra dependent fp64 products sit on the critical path -- and 2^18
-    // ties.  The stand-alone tree (pifft_tree_device) keeps the reference
-    // table and stays bitwise.  PIFFT_WIL_TREE_DIRECT=1: the reference table
-    // at every size (tuning, tests); PIFFT_WIL_TREE_MIN_LOG: the threshold.
-    bool wil_factored = false;
-    if (need_tree) {
-        const int direct_max = env_int("PIFFT_TREE_DIRECT_MAX_LOG", 22);
-        if (p->log_n <= direct_max) {
-            tree_is_direct = true;
-            tree_direct = tb.reference_omega_levels(p->n, p->lp);
-            // (and at P = 32, whose one-launch pass evaluates 16 workers' tree
-            // per thread: 80 dependent table lookups each, against 5: 2^10
-            // 12 -> 8 us, fp32 11 -> 6; P = 16 ties, profiles/r05p32b_*)
-            wil_factored = p->wil && env_int("PIFFT_WIL_TREE_DIRECT", 0) == 0 &&
-                           ((uint64_t)p->batch * p->n >= (1ull << env_int("PIFFT_WIL_TREE_MIN_LOG", 21)) || p->lp == 5);
-            if (wil_factored) tree2 = two_level(tb, p->n);
-        } else {
-            tree2 = two_level(tb, p->n);
-        }
-    }
-    // --- pass tables ---
-    std::vector<size_t> tw_r(passes.size());
-    for (size_t i = 0; i < passes.size(); i++) {
-        size_t found = (size_t)-1;
-        for (size_t j = 0; j < i; j++)
-            if (passes[j].R == passes[i].R) found = tw_r[j];
-        tw_r[i] = (found != (size_t)-1) ? found : tb.roots(passes[i].R, passes[i].R, 1);
-    }
-    TwoLevel pass2;
-    if (passes.size() > 1) pass2 = two_level(tb, p->m);  // (every worker-interleaved plan has >= 2 passes)
-    tb.align();
-    p->tw_bytes = tb.size() ? tb.size() : 256;
-    if (!dry) {
-        HIPCHK(hipMalloc(&p->d_tw, p->tw_bytes));
-        if (!tb.blob.empty()) HIPCHK(hipMemcpy(p->d_tw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
-    }
-    auto twp = [&](size_t off) { return (const void*)((const char*)p->d_tw + off); };
+    const bool fused = ch.fused != FUSED_NONE;
+    p->wil = ch.wil;
+    p->ilv = ch.ilv;
+    p->fused_tree = fused;
     TreeTw ttw{};
     if (need_tree) {
-        ttw.direct = tree_is_direct ? twp(tree_direct) : nullptr;
-        ttw.lo = tree_is_direct ? nullptr : twp(tree2.lo);
-        ttw.hi = tree_is_direct ? nullptr : twp(tree2.hi);
-        ttw.h = tree2.h;
+        ttw.h = tl.tree2.h;
         ttw.log_n = (uint32_t)p->log_n;
     }
-    // One worker on this plan, a multi-pass local FFT and log2 P <= 4: fuse the
-    // tree into the first pass (its P leaves per input instead of a separate
-    // tree launch that writes, and a pass that re-reads, the N/P segment).
-    const PassKernel* fused = nullptr;
-    if (may_fuse && passes.size() > 1)
-        fused = find_pass(p->prec, passes[0].R, passes[0].C, 3, passes[0].nts, p->lp, passes[0].vpt);
-    if (wil_fused_c) fused = find_pass(p->prec, passes[0].R, passes[0].C, 11, passes[0].nts, p->lp, passes[0].vpt);
-    p->fused_tree = fused != nullptr;
+    // the tree's twiddles: the reference table where the plan has one; the
+    // worker-interleaved plan's own tree (its k_tree_wil launch or its fused
+    // first pass) the two-level one from 2^21 values up (TREE_TW_WIL_FACTORED)
+    auto tree_tables = [&](Step& s, bool wil) {
+        const bool direct = tl.tree_direct != kNoTable && !(wil && ch.tree_tw == TREE_TW_WIL_FACTORED);
+        s.tab.tree_direct = direct ? tl.tree_direct : kNoTable;
+        s.tab.tree_lo = direct ? kNoTable : tl.tree2.lo;
+        s.tab.tree_hi = direct ? kNoTable : tl.tree2.hi;
+    };
 
-    // the worker-interleaved plan's tree twiddles (its k_tree_wil launch or
-    // its fused first pass): factored from 2^21 values up (wil_factored)
-    TreeTw wtw = ttw;
-    if (wil_factored) {
-        wtw.direct = nullptr;
-        wtw.lo = twp(tree2.lo);
-        wtw.hi = twp(tree2.hi);
-        wtw.h = tree2.h;
-    }
-
-    // --- chain: [tree] [passes] [interleave] ---
-    std::vector<Elem> chain;
+    // --- chain: [tree] [passes] [interleave]; an element's launches share its buffers ---
+    std::vector<std::vector<Step>> chain;
     const uint64_t M = p->m;
     if (need_tree) {
-        Elem e;
+        std::vector<Step> e;
         // ceil(log2 P / 4) launches of up to 4 levels each; in place over
         // one position-space buffer between launches (see k_tree)
         static const void* tk64[5] = {nullptr, (const void*)&k_tree<double, 1>, (const void*)&k_tree<double, 2>,
@@ -1061,6 +504,7 @@ int build_plan(pifft_plan* p, bool dry = false) {
             s.src = first ? -1 : BUF_TA;  // -1: chain input
             s.dst = last ? -2 : BUF_TA;   // -2: chain output (slice-major)
             s.ta.tw = ttw;
+            tree_tables(s, false);
             s.ta.in_bstride = p->n;
             s.ta.out_bstride = last ? (uint64_t)p->nq * M : p->n;
             s.ta.out_shift = last ? -(int64_t)((uint64_t)p->q0 * M) : 0;
@@ -1074,13 +518,13 @@ int build_plan(pifft_plan* p, bool dry = false) {
             s.grid = dim3(stride_grid(s.ta.total / (uint64_t)std::max(1, env_int("PIFFT_TREE_GRID_DIV", 1))));
             s.bytes = (uint64_t)p->batch * esz *
                       (blocks_needed(t0) * (p->n >> t0) + blocks_needed(t0 + L) * (p->n >> (t0 + L)));
-            e.steps.push_back(s);
+            e.push_back(s);
             t0 += L;
         }
         if (nl > 1) p->bytes_ta = (size_t)p->batch * p->n * esz;
         // the stand-alone tree (pifft_tree_device) reads d_in and writes d_seg
         // (slice-major, always)
-        for (Step t : e.steps) {
+        for (Step t : e) {
             if (t.src == -1) t.src = BUF_IN;
             if (t.dst == -2) t.dst = BUF_OUT;
             p->tree_only.push_back(t);
@@ -1090,46 +534,37 @@ int build_plan(pifft_plan* p, bool dry = false) {
                                           (const void*)&k_tree_wil<double, 3>, (const void*)&k_tree_wil<double, 4>};
             static const void* tw32[5] = {nullptr, (const void*)&k_tree_wil<float, 1>, (const void*)&k_tree_wil<float, 2>,
                                           (const void*)&k_tree_wil<float, 3>, (const void*)&k_tree_wil<float, 4>};
-            Step& t = e.steps.back();
+            Step& t = e.back();
             t.fn = p->prec == 64 ? tw64[p->lp] : tw32[p->lp];
-            t.ta.tw = wtw;
+            tree_tables(t, true);
             t.ta.out_bstride = p->n;
             t.lds = (size_t)tree_wil_pad(256u << p->lp) * esz;
-            if (t.lds > 65536 && !dry) (void)hipFuncSetAttribute(t.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds);
         }
         if (!fused) {
-            p->tree_steps = (int)e.steps.size();
+            p->tree_steps = (int)e.size();
             chain.push_back(e);
         }
     }
     uint64_t ns = 1;
-    p->npasses = (int)passes.size();
-    for (size_t i = 0; i < passes.size(); i++) {
+    p->npasses = (int)npass;
+    for (size_t i = 0; i < npass; i++) {
         const bool fuse_here = (i == 0 && fused);
-        const bool last_pass = i + 1 == passes.size() && passes.size() > 1;
-        // tuning: the last pass's streaming form (0 plain, 1 nt both, 2 nt loads, 3 nt stores)
-        int nt_override = last_pass && passes[i].mode == 2 ? env_int("PIFFT_LAST_NT", -1) : -1;
-        // (and the first pass's, 0 plain / 1 nt both, of a plan without a fused tree; round 6,
-        // profiles/r06y3_*: the default stays)
-        if (i == 0 && !fuse_here && passes.size() > 1 && passes[i].mode == 1)
-            nt_override = env_int("PIFFT_FIRST_NT", -1);
-        const PassKernel* k = fuse_here ? fused
-                                        : find_pass(p->prec, passes[i].R, passes[i].C, passes[i].mode,
-                                                    nt_override >= 0 ? nt_override : passes[i].nts, 0, passes[i].vpt);
-        if (!k) return fail("no pass kernel R=%d C=%d", passes[i].R, passes[i].C);
+        const bool last_pass = i + 1 == npass && npass > 1;
+        const PassKernel* k = ch.passes[i];
         Step s;
         s.kind = fuse_here ? STEP_TREE_PASS : STEP_PASS;
         s.fn = k->fn;
         s.pk = k;
         s.nts = k->nts;
         const int logr = ilog2u((uint64_t)k->R);
-        s.pa.tw_r = twp(tw_r[i]);
-        s.pa.tw_lo = passes.size() > 1 ? twp(pass2.lo) : nullptr;
-        s.pa.tw_hi = passes.size() > 1 ? twp(pass2.hi) : nullptr;
-        s.pa.tw_h = pass2.h;
+        s.tab.r = tl.tw_r[i];
+        s.tab.lo = tl.pass2.lo;
+        s.tab.hi = tl.pass2.hi;
+        s.pa.tw_h = tl.pass2.h;
         s.pa.in_bstride = (i == 0 && (!need_tree || fuse_here)) ? p->n : M;
         if (fuse_here) {
-            s.pa.tree = p->wil ? wtw : ttw;
+            s.pa.tree = ttw;
+            tree_tables(s, p->wil);
             s.pa.worker = p->q0;
             s.pa.log_nq = (uint32_t)ilog2u(p->nq);
         }
@@ -1138,39 +573,32 @@ int build_plan(pifft_plan* p, bool dry = false) {
         s.pa.log_lb = (uint32_t)(p->log_m - logr);
         s.pa.log_ns = (uint32_t)ilog2u(ns);
         s.pa.tw_shift = (uint32_t)(p->log_m - ilog2u(ns) - logr);
-        s.pa.log_xg = (uint32_t)env_int((passes[i].mode & 3) == 0 ? "PIFFT_XCD_GROUP_SINGLE" : "PIFFT_XCD_GROUP",
-                                        (passes[i].mode & 3) == 0 ? 0 : 2);
+        s.pa.log_xg = (uint32_t)env_int((k->mode & 3) == 0 ? "PIFFT_XCD_GROUP_SINGLE" : "PIFFT_XCD_GROUP",
+                                        (k->mode & 3) == 0 ? 0 : 2);
         if (last_pass) s.pa.log_xg = (uint32_t)env_int("PIFFT_LAST_XCD_GROUP", (int)s.pa.log_xg);
         if (p->wil) {
             s.pa.wil = (uint32_t)p->lp;
-            s.pa.wbrev = (i + 1 == passes.size()) ? 1u : 0u;  // the last pass: natural order
-            s.pa.in_bstride = s.pa.out_bstride = p->n;          // a transform's P interleaved workers
+            s.pa.wbrev = (i + 1 == npass) ? 1u : 0u;  // the last pass: natural order
+            s.pa.in_bstride = s.pa.out_bstride = p->n;  // a transform's P interleaved workers
         }
-        if (p->ilv && i + 1 == passes.size()) {
+        if (p->ilv && i + 1 == npass) {
             s.pa.ilv_log = (uint32_t)p->lp;
             s.pa.out_bstride = p->n;
             s.pa.log_xg = std::max<uint32_t>(s.pa.log_xg, (uint32_t)env_int("PIFFT_ILV_XCD_GROUP", p->lp));
         }
         s.block = dim3((unsigned)k->nt);
-        const uint64_t wgs = (s.pa.nlines + (uint64_t)k->C - 1) / (uint64_t)k->C;
-        if (wgs * (uint64_t)k->nt >= (1ull << 32)) return fail("transform too large for one launch (%llu work-items)",
-                                                             (unsigned long long)(wgs * k->nt));
-        s.grid = dim3((unsigned)wgs);
+        s.grid = dim3((unsigned)((s.pa.nlines + (uint64_t)k->C - 1) / (uint64_t)k->C));  // (< 2^32 work-items: choose_plan)
         s.lds = (size_t)k->lds_bytes;
         // (a one-worker fused pass reads every leaf of its worker's transform:
         // N per worker; the all-worker one, MODE 11, each leaf once)
         s.bytes = (!fuse_here || p->wil) ? 2 * ntrans * M * esz : (uint64_t)p->batch * p->nq * (p->n + M) * esz;
-        if (s.lds > 65536 && !dry)
-            (void)hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
         if (i < 8) {
             p->radix[i] = k->R;
             p->lines[i] = k->C;
             p->vpt[i] = k->vpt;
         }
         ns *= (uint64_t)k->R;
-        Elem e;
-        e.steps.push_back(s);
-        chain.push_back(e);
+        chain.push_back({s});
     }
     if (p->natural && p->P > 1 && !p->ilv && !p->wil) {
         Step s;
@@ -1182,9 +610,7 @@ int build_plan(pifft_plan* p, bool dry = false) {
         s.block = dim3(256);
         s.grid = dim3(stride_grid(interleave_threads(s.il_total, p->lp, p->prec, p->n)));
         s.bytes = 2 * s.il_total * esz;
-        Elem e;
-        e.steps.push_back(s);
-        chain.push_back(e);
+        chain.push_back({s});
     }
     if (chain.empty()) return fail("empty plan");
     // destinations, backwards: last -> OUT, then W, OUT, W, ...
@@ -1194,7 +620,7 @@ int build_plan(pifft_plan* p, bool dry = false) {
     for (size_t i = 0; i < chain.size(); i++) {
         const int src = (i == 0) ? BUF_IN : dst[i - 1];
         if (dst[i] == BUF_W || src == BUF_W) need_w = true;
-        for (auto& s : chain[i].steps) {
+        for (auto& s : chain[i]) {
             if (s.src == -1) s.src = src;
             if (s.dst == -2) s.dst = dst[i];
             p->steps.push_back(s);
@@ -1232,7 +658,72 @@ int build_plan(pifft_plan* p, bool dry = false) {
         }
     }
     p->bytes_w = need_w ? (size_t)p->batch * p->nq * w_tr * esz : 0;
-    if (dry) return 0;
+    return 0;
+}
+
+// the one added launch of a real plan (create_real), after the inner chain is
+// final: its w_N^k table, k <= N/4, two-level at every size -- 2^h ~ sqrt N
+// entries per level (256 KiB each at fp64 2^28), against N/4 + 1 of a direct
+// table -- joins the plan's blob
+void add_real_step(pifft_plan* p, TableBuilder& tb, uint64_t n, bool c2r) {
+    const uint64_t H = n / 2;
+    p->real = c2r ? 2 : 1;
+    p->real_n = n;
+    p->bytes_z = (size_t)p->batch * H * p->esz;
+    const size_t before = tb.size();
+    const TwoLevel tw = two_level(tb, n);
+    tb.align();
+    p->rtw_bytes = tb.size() - before;
+    Step s;
+    s.kind = c2r ? STEP_C2R_PRE : STEP_R2C_POST;
+    s.fn = p->prec == PIFFT_F64 ? (c2r ? (const void*)&k_c2r_pre<double> : (const void*)&k_r2c_post<double>)
+                                : (c2r ? (const void*)&k_c2r_pre<float> : (const void*)&k_r2c_post<float>);
+    s.tab.lo = tw.lo;
+    s.tab.hi = tw.hi;
+    s.ra.tw_h = tw.h;
+    s.ra.batch = p->batch;
+    s.ra.h = H;
+    s.ra.units = p->prec == PIFFT_F64 ? real_units<double>(H) : real_units<float>(H);
+    s.block = dim3(256);
+    s.grid = dim3(stride_grid((uint64_t)p->batch * s.ra.units));
+    const uint64_t threads = (uint64_t)s.grid.x * 256;
+    s.ra.step_rows = threads / s.ra.units;
+    s.ra.step_units = threads % s.ra.units;
+    s.bytes = (uint64_t)p->batch * (2 * H + 1) * p->esz;
+    if (c2r) {
+        s.src = BUF_IN;
+        s.dst = BUF_Z;
+        for (Step& t : p->steps)
+            if (t.src == BUF_IN) t.src = BUF_Z;
+        p->steps.insert(p->steps.begin(), s);
+    } else {
+        for (Step& t : p->steps) {
+            if (t.src == BUF_OUT) t.src = BUF_Z;
+            if (t.dst == BUF_OUT) t.dst = BUF_Z;
+        }
+        s.src = BUF_Z;
+        s.dst = BUF_OUT;
+        p->steps.push_back(s);
+    }
+    p->tree_only.clear();  // (pifft_tree_device refuses real plans)
+}
+
+// Step 4, real (non-dry) plans only: the table blob on the device and every
+// step's offsets resolved to pointers into it, the plan's buffers, stream and
+// events, and the LDS attribute of the kernels the final steps launch.
+int materialise(pifft_plan* p, const TableBuilder& tb) {
+    HIPCHK(hipMalloc(&p->d_tw, p->tw_bytes + p->rtw_bytes));
+    if (!tb.blob.empty()) HIPCHK(hipMemcpy(p->d_tw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
+    auto at = [&](size_t off) { return off == kNoTable ? nullptr : (const void*)((const char*)p->d_tw + off); };
+    auto resolve = [&](Step& s) {
+        TreeTw& tree = s.kind == STEP_TREE ? s.ta.tw : s.pa.tree;
+        tree.direct = at(s.tab.tree_direct), tree.lo = at(s.tab.tree_lo), tree.hi = at(s.tab.tree_hi);
+        if (s.kind == STEP_R2C_POST || s.kind == STEP_C2R_PRE) s.ra.tw_lo = at(s.tab.lo), s.ra.tw_hi = at(s.tab.hi);
+        else s.pa.tw_r = at(s.tab.r), s.pa.tw_lo = at(s.tab.lo), s.pa.tw_hi = at(s.tab.hi);
+        if (s.lds > 65536) (void)hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
+    };
+    for (Step& s : p->steps) resolve(s);
+    for (Step& s : p->tree_only) resolve(s);
     // tuning knob (tools/probe_place.py): hipExtMallocWithFlags flags for the
     // ping-pong workspace, e.g. 4 = hipDeviceMallocContiguous
     const int w_flags = env_int("PIFFT_W_MALLOC_FLAGS", 0);
@@ -1240,6 +731,7 @@ int build_plan(pifft_plan* p, bool dry = false) {
         HIPCHK(w_flags ? hipExtMallocWithFlags(&p->buf[BUF_W], p->bytes_w, (unsigned)w_flags)
                        : hipMalloc(&p->buf[BUF_W], p->bytes_w));
     if (p->bytes_ta) HIPCHK(hipMalloc(&p->buf[BUF_TA], p->bytes_ta));
+    if (p->bytes_z) HIPCHK(hipMalloc(&p->buf[BUF_Z], p->bytes_z));
     HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     p->ev.resize(2 * p->steps.size());
     for (auto& e : p->ev) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
@@ -1254,7 +746,7 @@ int build_plan(pifft_plan* p, bool dry = false) {
 // caller's output its twin swapping what it stores (one launch: both).  No
 // launch, byte or table more; the result equals swap(forward(swap(x))) bit
 // for bit.  Step::pk keeps the forward instance the twin derives from.
-int make_inverse(pifft_plan* p, bool dry) {
+int make_inverse(pifft_plan* p) {
     if (p->steps.empty()) return fail("empty plan");
     const size_t last = p->steps.size() - 1;
     if (p->steps[0].src != BUF_IN || p->steps[last].dst != BUF_OUT) return fail("inverse plan: unexpected buffer chain");
@@ -1277,58 +769,60 @@ int make_inverse(pifft_plan* p, bool dry) {
                                 s.kind == STEP_TREE ? "tree" : "interleave", i);
             s.fn = t;
         }
-        if (s.lds > 65536 && !dry)
-            (void)hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
     }
     return 0;
 }
 
-int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint32_t count,
-           uint32_t batch, int prec, int device, int flags, bool dry = false) {
+// choose (pifft_planner.h), lay out the tables, assemble the launches; then,
+// unless dry (pifft_plan_dry_run: no device, no allocation), materialise.
+// real_n: the real length of a real plan (its added launch), else 0
+int build_plan(pifft_plan* p, bool dry, uint64_t real_n = 0) {
+    PlanChoice ch;
+    if (choose_plan(*p, ch)) return -1;
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    const TableLayout tl = layout_tables(*p, ch, tb);
+    p->tw_bytes = tb.size() ? tb.size() : 256;
+    if (assemble_steps(p, ch, tl) || (p->inverse && make_inverse(p))) return -1;
+    if (real_n) add_real_step(p, tb, real_n, p->inverse);
+    return dry ? 0 : materialise(p, tb);
+}
+
+// the checks every plan shares; real: a real plan of n reals (create_real),
+// which splits its n/2-point transform
+int check_args(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch, int prec,
+               bool real) {
     if (!out) return fail("plan pointer is NULL");
     *out = nullptr;
+    if (real && (n < 4 || !is_pow2(n))) return fail("Invalid input size (a real plan needs 2^i reals, i > 1)");
     if (n < 2 || !is_pow2(n)) return fail("Invalid input size (should be 2^i for i>0)");
     if (workers == 0 || !is_pow2(workers)) return fail("Invalid number of procs (should be 2^i for i>0)");
+    if (real && workers > n / 2) return fail("More processors than inputs! (a real plan splits its n/2-point transform)");
     if (workers > n) return fail("More processors than inputs!");
     if (count == 0 || !is_pow2(count) || first % count != 0 || (uint64_t)first + count > workers)
         return fail("invalid worker range [%u, %u) of %u", first, first + count, workers);
     if (batch == 0) return fail("batch must be >= 1");
     if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
-    const int order = flags & ~(PIFFT_SEPARATE_TREE | PIFFT_INVERSE);
-    if (order != PIFFT_OUT_NATURAL && order != PIFFT_OUT_SLICES && order != PIFFT_OUT_BITREV)
-        return fail("unknown flags %d", flags);
-    // (flags name an order for a worker range: the value is as unknown for a
-    // partial range -- PIFFT_INVERSE alone, say, which implies natural order --
-    // as an undefined bit is, and the message says which rule it broke)
-    if (order == PIFFT_OUT_NATURAL && count != workers)
-        return fail("unknown flags %d for workers [%u, %u) of %u: natural-order output needs all workers on one plan "
-                    "(use PIFFT_OUT_SLICES)", flags, first, first + count, workers);
+    return 0;
+}
+
+// n: the complex transform's length; real_n: see build_plan
+int create_checked(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch,
+                   int prec, int device, int flags, bool dry, uint64_t real_n = 0) {
     if (!dry) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available");
         if (device < 0 || device >= ndev) return fail("device %d out of range (%d devices)", device, ndev);
     }
+    const int order = flags & ~(PIFFT_SEPARATE_TREE | PIFFT_INVERSE);
     pifft_plan* p = new pifft_plan;
-    p->n = n;
-    p->P = workers;
-    p->q0 = first;
-    p->nq = count;
-    p->batch = batch;
-    p->prec = prec;
-    p->device = device;
+    static_cast<PlanShape&>(*p) = plan_shape(n, workers, first, count, batch, prec, order == PIFFT_OUT_NATURAL,
+                                             order == PIFFT_OUT_BITREV, (flags & PIFFT_SEPARATE_TREE) != 0);
+    p->device = dry ? -1 : device;
     p->flags = flags;
-    p->natural = (order == PIFFT_OUT_NATURAL);
-    p->bitrev = (order == PIFFT_OUT_BITREV);
-    p->separate_tree = (flags & PIFFT_SEPARATE_TREE) != 0;
     p->inverse = (flags & PIFFT_INVERSE) != 0;
-    p->esz = prec == PIFFT_F64 ? 16 : 8;
-    p->lp = ilog2u(workers);
-    p->log_n = ilog2u(n);
-    p->log_m = p->log_n - p->lp;
-    p->m = n >> p->lp;
-    if (dry) p->device = -1;
-    DeviceGuard g(dry ? -1 : device);
-    if (build_plan(p, dry) || (p->inverse && make_inverse(p, dry))) {
+    DeviceGuard g(p->device);
+    if (build_plan(p, dry, real_n)) {
         std::string keep = g_err;
         release(p);
         g_err = keep;
@@ -1338,11 +832,26 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
     return 0;
 }
 
+int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint32_t count,
+           uint32_t batch, int prec, int device, int flags, bool dry = false) {
+    if (check_args(out, n, workers, first, count, batch, prec, false)) return -1;
+    const int order = flags & ~(PIFFT_SEPARATE_TREE | PIFFT_INVERSE);
+    if (order != PIFFT_OUT_NATURAL && order != PIFFT_OUT_SLICES && order != PIFFT_OUT_BITREV)
+        return fail("unknown flags %d", flags);
+    // (flags name an order for a worker range: the value is as unknown for a
+    // partial range -- PIFFT_INVERSE alone, say, which implies natural order --
+    // as an undefined bit is, and the message says which rule it broke)
+    if (order == PIFFT_OUT_NATURAL && count != workers)
+        return fail("unknown flags %d for workers [%u, %u) of %u: natural-order output needs all workers on one plan "
+                    "(use PIFFT_OUT_SLICES)", flags, first, first + count, workers);
+    return create_checked(out, n, workers, first, count, batch, prec, device, flags, dry);
+}
+
 // Real-input plans (pifft_plan_create_real; kernels and formulas in
 // pifft_real.h).  The N reals are the H = N/2 complex values z[n] = x[2n] +
 // i x[2n+1] as they lie in memory, so the plan is the complex plan build_plan
-// makes for (H, P, all workers, natural order) -- untouched, whatever it
-// chooses for that shape -- plus one streaming launch:
+// makes for (H, P, all workers, natural order) -- untouched, whatever
+// choose_plan picks for that shape -- plus one streaming launch (add_real_step):
 //   R2C: [inner forward chain: d_in -> Z] [k_r2c_post: Z -> d_out]
 //   C2R: [k_c2r_pre: d_in -> Z] [inner inverse chain (make_inverse): Z -> d_out]
 // Z (BUF_Z, batch x H values) is plan-owned: the inner chain of an R2C plan
@@ -1353,82 +862,12 @@ int create(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t first, uint3
 // always holds all P workers.
 int create_real(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t batch, int prec, int device, int direction,
                 bool dry = false) {
-    if (!out) return fail("plan pointer is NULL");
-    *out = nullptr;
-    if (n < 4 || !is_pow2(n)) return fail("Invalid input size (a real plan needs 2^i reals, i > 1)");
-    if (workers == 0 || !is_pow2(workers)) return fail("Invalid number of procs (should be 2^i for i>0)");
-    if (workers > n / 2) return fail("More processors than inputs! (a real plan splits its n/2-point transform)");
-    if (batch == 0) return fail("batch must be >= 1");
-    if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
+    if (check_args(out, n, workers, 0, workers, batch, prec, true)) return -1;
     if (direction != PIFFT_REAL_FORWARD && direction != PIFFT_REAL_INVERSE)
         return fail("direction must be PIFFT_REAL_FORWARD or PIFFT_REAL_INVERSE");
     const bool c2r = direction == PIFFT_REAL_INVERSE;
-    const uint64_t H = n / 2;
-    pifft_plan* p = nullptr;
-    if (create(&p, H, workers, 0, workers, batch, prec, device, PIFFT_OUT_NATURAL | (c2r ? PIFFT_INVERSE : 0), dry))
-        return -1;
-    p->real = c2r ? 2 : 1;
-    p->real_n = n;
-    p->bytes_z = (size_t)batch * H * p->esz;
-    // w_N^k, k <= N/4, two-level at every size: 2^h ~ sqrt N entries per
-    // level (256 KiB each at fp64 2^28), against N/4 + 1 of a direct table
-    TableBuilder tb(p->esz);
-    tb.size_only = dry;
-    const TwoLevel tw = two_level(tb, n);
-    tb.align();
-    p->rtw_bytes = tb.size();
-    DeviceGuard g(dry ? -1 : device);
-    if (!dry) {
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        if (hipMalloc(&p->buf[BUF_Z], p->bytes_z) != hipSuccess || hipMalloc(&p->d_rtw, p->rtw_bytes) != hipSuccess ||
-            hipMemcpy(p->d_rtw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipEventCreateWithFlags(&ev[0], kTimingEventFlags) != hipSuccess ||
-            hipEventCreateWithFlags(&ev[1], kTimingEventFlags) != hipSuccess) {
-            const hipError_t err = hipGetLastError();
-            for (auto e : ev)
-                if (e) (void)hipEventDestroy(e);
-            const size_t want = p->bytes_z;
-            release(p);
-            return fail("real plan: allocating the staging buffer (%zu bytes), table or events failed: %s", want,
-                        hipGetErrorString(err));
-        }
-        p->ev.push_back(ev[0]);  // the added launch's start and stop
-        p->ev.push_back(ev[1]);
-    }
-    Step s;
-    s.kind = c2r ? STEP_C2R_PRE : STEP_R2C_POST;
-    s.fn = prec == PIFFT_F64 ? (c2r ? (const void*)&k_c2r_pre<double> : (const void*)&k_r2c_post<double>)
-                             : (c2r ? (const void*)&k_c2r_pre<float> : (const void*)&k_r2c_post<float>);
-    s.ra.tw_lo = dry ? nullptr : (const void*)((const char*)p->d_rtw + tw.lo);
-    s.ra.tw_hi = dry ? nullptr : (const void*)((const char*)p->d_rtw + tw.hi);
-    s.ra.tw_h = tw.h;
-    s.ra.batch = batch;
-    s.ra.h = H;
-    s.ra.units = prec == PIFFT_F64 ? real_units<double>(H) : real_units<float>(H);
-    s.block = dim3(256);
-    s.grid = dim3(stride_grid((uint64_t)batch * s.ra.units));
-    const uint64_t threads = (uint64_t)s.grid.x * 256;
-    s.ra.step_rows = threads / s.ra.units;
-    s.ra.step_units = threads % s.ra.units;
-    s.bytes = (uint64_t)batch * (2 * H + 1) * p->esz;
-    if (c2r) {
-        s.src = BUF_IN;
-        s.dst = BUF_Z;
-        for (Step& t : p->steps)
-            if (t.src == BUF_IN) t.src = BUF_Z;
-        p->steps.insert(p->steps.begin(), s);
-    } else {
-        for (Step& t : p->steps) {
-            if (t.src == BUF_OUT) t.src = BUF_Z;
-            if (t.dst == BUF_OUT) t.dst = BUF_Z;
-        }
-        s.src = BUF_Z;
-        s.dst = BUF_OUT;
-        p->steps.push_back(s);
-    }
-    p->tree_only.clear();  // (pifft_tree_device refuses real plans)
-    *out = p;
-    return 0;
+    return create_checked(out, n / 2, workers, 0, workers, batch, prec, device,
+                          PIFFT_OUT_NATURAL | (c2r ? PIFFT_INVERSE : 0), dry, n);
 }
 
 const char* kRealOnly = "real plans (pifft_plan_create_real) run through pifft_execute_device, "

@@ -1645,87 +1645,61 @@ struct TreeArgs {
     uint32_t q0, nq;        // workers [q0, q0+nq)
 };
 
+// The tree and interleave kernels share one textual body each with their
+// swapping twins (inverse plans): PIFFT_*_BODY(SW), expanded at SW = 0 in the
+// forward kernel and at SW (1: swaps the loads of the caller's input, 2: the
+// stores to the caller's output, 3: both) in the twin, as
+// PIFFT_PASS_KERNEL_BODY.  Textual, not a __device__ function: behind a
+// function call the forward kernels compiled to different (equivalent) code
+// -- launch geometry reads and kernel-argument loads are lowered differently
+// -- and the forward code objects must not move.
+//
+// k_tree -- grid-stride (a launch's work-item count must stay below 2^32);
+// 2^log_g threads per transform, D = 2^log_d between a thread's positions,
+// 2^log_w workers below one level-(t0+L) block; groups with no requested
+// worker below them are skipped.  No __restrict__ on src/dst: launches after
+// the first of a multi-launch tree (log2 P > 4) run in place; each thread
+// reads and writes only its own 2^L positions.
+#define PIFFT_TREE_BODY(SW)                                                                                           \
+    using C2 = cx<T>;                                                                                                 \
+    constexpr int V = 1 << L;                                                                                         \
+    for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < a.total;                               \
+         gid += (uint64_t)gridDim.x * blockDim.x) {                                                                   \
+        const uint32_t log_g = a.log_n - L;                                                                           \
+        const uint32_t log_d = a.log_n - a.t0 - L;                                                                    \
+        const uint64_t g = gid & ((1ull << log_g) - 1), bt = gid >> log_g;                                            \
+        const uint64_t blk0 = g >> log_d, i = g & ((1ull << log_d) - 1);                                              \
+        const uint64_t base = blk0 << (a.log_n - a.t0);                                                               \
+        const uint32_t log_w = a.log_p - a.t0 - L;                                                                    \
+        const uint64_t q0 = a.q0, q1 = (uint64_t)a.q0 + a.nq;                                                         \
+        const uint64_t w_lo = (blk0 << L) << log_w, w_hi = ((blk0 + 1) << L) << log_w;                                \
+        if (w_hi <= q0 || w_lo >= q1) continue;                                                                       \
+        const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + base + i;                                  \
+        C2 v[V];                                                                                                      \
+        _Pragma("unroll") for (int m = 0; m < V; m++) {                                                               \
+            if constexpr ((SW) & 1) v[m] = sw_in<(SW)>(src[(uint64_t)m << log_d]);                                    \
+            else v[m] = src[(uint64_t)m << log_d];                                                                    \
+        }                                                                                                             \
+        tree_levels<T, L>(v, a.tw, i, log_d, a.t0, blk0, log_w, q0, q1);                                              \
+        C2* dst = static_cast<C2*>(a.out) + bt * a.out_bstride + (int64_t)(base + i) + a.out_shift;                   \
+        _Pragma("unroll") for (int m = 0; m < V; m++) {                                                               \
+            const uint64_t wm = ((blk0 << L) + m) << log_w;                                                           \
+            if (wm < q1 && wm + (1ull << log_w) > q0) {                                                               \
+                if constexpr ((SW) & 2) dst[(uint64_t)m << log_d] = sw_out<(SW)>(v[m]);                               \
+                else dst[(uint64_t)m << log_d] = v[m];                                                                \
+            }                                                                                                         \
+        }                                                                                                             \
+    }
 template <typename T, int L>
 __global__ __launch_bounds__(256) void k_tree(TreeArgs a) {
-    using C2 = cx<T>;
-    constexpr int V = 1 << L;
-    // grid-stride: the work-item count of one launch must stay below 2^32
-    for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < a.total;
-         gid += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t log_g = a.log_n - L;            // threads per transform = 2^log_g
-    const uint32_t log_d = a.log_n - a.t0 - L;     // D = stride between a thread's positions
-    const uint64_t g = gid & ((1ull << log_g) - 1), bt = gid >> log_g;
-    const uint64_t blk0 = g >> log_d, i = g & ((1ull << log_d) - 1);
-    const uint64_t base = blk0 << (a.log_n - a.t0);
-    const uint32_t log_w = a.log_p - a.t0 - L;     // workers below one level-(t0+L) block
-    const uint64_t q0 = a.q0, q1 = (uint64_t)a.q0 + a.nq;
-    const uint64_t w_lo = (blk0 << L) << log_w, w_hi = ((blk0 + 1) << L) << log_w;
-    if (w_hi <= q0 || w_lo >= q1) continue;  // no requested worker below this group
-    // no __restrict__ on src/dst: launches after the first of a multi-launch
-    // tree (log2 P > 4) run in place (src == dst == the plan's tree buffer);
-    // each thread reads and writes only its own 2^L positions
-    const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + base + i;
-    C2 v[V];
-#pragma unroll
-    for (int m = 0; m < V; m++) v[m] = src[(uint64_t)m << log_d];
-    tree_levels<T, L>(v, a.tw, i, log_d, a.t0, blk0, log_w, q0, q1);
-    C2* dst = static_cast<C2*>(a.out) + bt * a.out_bstride + (int64_t)(base + i) + a.out_shift;
-#pragma unroll
-    for (int m = 0; m < V; m++) {
-        const uint64_t wm = ((blk0 << L) + m) << log_w;
-        if (wm < q1 && wm + (1ull << log_w) > q0) dst[(uint64_t)m << log_d] = v[m];
-    }
-    }  // grid-stride
-}
-// The swapping twin's body (inverse plans): k_tree's own statements with SW's
-// swaps.  The forward kernel above keeps its text: compiled as a call of this
-// body at SW = 0 it came out as different (equivalent) code -- the launch
-// geometry reads and the kernel-argument loads are lowered differently behind
-// a __device__ function -- and the forward code objects must not move.  Keep
-// the two in step.
-template <typename T, int L, int SW>
-__device__ __forceinline__ void tree_body(const TreeArgs& a, const uint32_t bdim, const uint32_t gdim) {
-    using C2 = cx<T>;
-    constexpr int V = 1 << L;
-    // grid-stride: the work-item count of one launch must stay below 2^32
-    for (uint64_t gid = (uint64_t)blockIdx.x * bdim + threadIdx.x; gid < a.total;
-         gid += (uint64_t)gdim * bdim) {
-    const uint32_t log_g = a.log_n - L;            // threads per transform = 2^log_g
-    const uint32_t log_d = a.log_n - a.t0 - L;     // D = stride between a thread's positions
-    const uint64_t g = gid & ((1ull << log_g) - 1), bt = gid >> log_g;
-    const uint64_t blk0 = g >> log_d, i = g & ((1ull << log_d) - 1);
-    const uint64_t base = blk0 << (a.log_n - a.t0);
-    const uint32_t log_w = a.log_p - a.t0 - L;     // workers below one level-(t0+L) block
-    const uint64_t q0 = a.q0, q1 = (uint64_t)a.q0 + a.nq;
-    const uint64_t w_lo = (blk0 << L) << log_w, w_hi = ((blk0 + 1) << L) << log_w;
-    if (w_hi <= q0 || w_lo >= q1) continue;  // no requested worker below this group
-    // no __restrict__ on src/dst: launches after the first of a multi-launch
-    // tree (log2 P > 4) run in place (src == dst == the plan's tree buffer);
-    // each thread reads and writes only its own 2^L positions
-    const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + base + i;
-    C2 v[V];
-#pragma unroll
-    for (int m = 0; m < V; m++) {
-        if constexpr (SW & 1) v[m] = sw_in<SW>(src[(uint64_t)m << log_d]);
-        else v[m] = src[(uint64_t)m << log_d];
-    }
-    tree_levels<T, L>(v, a.tw, i, log_d, a.t0, blk0, log_w, q0, q1);
-    C2* dst = static_cast<C2*>(a.out) + bt * a.out_bstride + (int64_t)(base + i) + a.out_shift;
-#pragma unroll
-    for (int m = 0; m < V; m++) {
-        const uint64_t wm = ((blk0 << L) + m) << log_w;
-        if (wm < q1 && wm + (1ull << log_w) > q0) {
-            if constexpr (SW & 2) dst[(uint64_t)m << log_d] = sw_out<SW>(v[m]);
-            else dst[(uint64_t)m << log_d] = v[m];
-        }
-    }
-    }  // grid-stride
+    PIFFT_TREE_BODY(0);
 }
 // inverse plans: the tree launch that reads the caller's input (SW 1), writes
 // the caller's output (SW 2: M = 1, the last tree launch) or both (SW 3)
 template <typename T, int L, int SW>
 __global__ __launch_bounds__(256) void k_tree_sw(TreeArgs a) {
-    tree_body<T, L, SW>(a, blockDim.x, gridDim.x);
+    static_assert(SW >= 1 && SW <= 3, "k_tree_sw: a swapping twin (the forward kernel is k_tree)");
+    PIFFT_TREE_BODY(SW);
 }
 
 // The single launch of an all-worker tree (t0 = 0, all P = 2^L workers)
@@ -1736,123 +1710,67 @@ __global__ __launch_bounds__(256) void k_tree_sw(TreeArgs a) {
 // writes 64 consecutive values instead of 64 pieces P values apart.
 // Dynamic LDS: 256 P (9/8) values.
 __host__ __device__ constexpr uint32_t tree_wil_pad(uint32_t idx) { return idx + (idx >> 3); }
+// (2^log_d = M threads per transform; a block-uniform loop, every thread reaches
+// the barriers -- the first: the previous round's reads of `stage` are done)
+#define PIFFT_TREE_WIL_BODY(SW)                                                                                       \
+    using C2 = cx<T>;                                                                                                 \
+    constexpr int V = 1 << L;                                                                                         \
+    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];                                        \
+    C2* stage = reinterpret_cast<C2*>(pifft_smem);                                                                    \
+    const uint32_t log_d = a.log_n - L;                                                                               \
+    const uint64_t nblk = (a.total + 255) / 256;                                                                      \
+    for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {                                                   \
+        const uint64_t g0 = blk * 256, gid = g0 + threadIdx.x;                                                        \
+        const uint64_t g = gid < a.total ? gid : a.total - 1;                                                         \
+        const uint64_t bt = g >> log_d, i = g & ((1ull << log_d) - 1);                                                \
+        const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + i;                                         \
+        C2 v[V];                                                                                                      \
+        _Pragma("unroll") for (int m = 0; m < V; m++) {                                                               \
+            if constexpr ((SW) & 1) v[m] = sw_in<(SW)>(src[(uint64_t)m << log_d]);                                    \
+            else v[m] = src[(uint64_t)m << log_d];                                                                    \
+        }                                                                                                             \
+        tree_levels<T, L>(v, a.tw, i, log_d, 0, 0, 0, 0, V);                                                          \
+        __syncthreads();                                                                                              \
+        _Pragma("unroll") for (int m = 0; m < V; m++) stage[tree_wil_pad(threadIdx.x * V + m)] = v[m];                \
+        __syncthreads();                                                                                              \
+        const uint64_t b0 = g0 >> log_d, i0 = g0 & ((1ull << log_d) - 1);                                             \
+        C2* dst = static_cast<C2*>(a.out) + b0 * a.out_bstride + (i0 << L);                                           \
+        const uint64_t nvalid = (a.total - g0 < 256 ? a.total - g0 : 256) * V;                                        \
+        _Pragma("unroll") for (int k = 0; k < V; k++) {                                                               \
+            const uint32_t idx = (uint32_t)k * 256 + threadIdx.x;                                                     \
+            if (idx < nvalid) dst[idx] = stage[tree_wil_pad(idx)];                                                    \
+        }                                                                                                             \
+    }
 template <typename T, int L>
 __global__ __launch_bounds__(256) void k_tree_wil(TreeArgs a) {
-    using C2 = cx<T>;
-    constexpr int V = 1 << L;
-    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];
-    C2* stage = reinterpret_cast<C2*>(pifft_smem);
-    const uint32_t log_d = a.log_n - L;  // 2^log_d = M threads per transform
-    const uint64_t nblk = (a.total + 255) / 256;
-    // (block-uniform loop: every thread of a block reaches the barriers)
-    for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        const uint64_t g0 = blk * 256, gid = g0 + threadIdx.x;
-        const uint64_t g = gid < a.total ? gid : a.total - 1;
-        const uint64_t bt = g >> log_d, i = g & ((1ull << log_d) - 1);
-        const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + i;
-        C2 v[V];
-#pragma unroll
-        for (int m = 0; m < V; m++) v[m] = src[(uint64_t)m << log_d];
-        tree_levels<T, L>(v, a.tw, i, log_d, 0, 0, 0, 0, V);
-        __syncthreads();  // the previous round's reads of `stage` are done
-#pragma unroll
-        for (int m = 0; m < V; m++) stage[tree_wil_pad(threadIdx.x * V + m)] = v[m];
-        __syncthreads();
-        const uint64_t b0 = g0 >> log_d, i0 = g0 & ((1ull << log_d) - 1);
-        C2* dst = static_cast<C2*>(a.out) + b0 * a.out_bstride + (i0 << L);
-        const uint64_t nvalid = (a.total - g0 < 256 ? a.total - g0 : 256) * V;
-#pragma unroll
-        for (int k = 0; k < V; k++) {
-            const uint32_t idx = (uint32_t)k * 256 + threadIdx.x;
-            if (idx < nvalid) dst[idx] = stage[tree_wil_pad(idx)];
-        }
-    }
-}
-// The swapping twin's body (inverse plans): k_tree_wil's own statements with SW's
-// swaps.  The forward kernel above keeps its text: compiled as a call of this
-// body at SW = 0 it came out as different (equivalent) code -- the launch
-// geometry reads and the kernel-argument loads are lowered differently behind
-// a __device__ function -- and the forward code objects must not move.  Keep
-// the two in step.
-template <typename T, int L, int SW>
-__device__ __forceinline__ void tree_wil_body(const TreeArgs& a, const uint32_t gdim) {
-    using C2 = cx<T>;
-    constexpr int V = 1 << L;
-    extern __shared__ __attribute__((aligned(16))) unsigned char pifft_smem[];
-    C2* stage = reinterpret_cast<C2*>(pifft_smem);
-    const uint32_t log_d = a.log_n - L;  // 2^log_d = M threads per transform
-    const uint64_t nblk = (a.total + 255) / 256;
-    // (block-uniform loop: every thread of a block reaches the barriers)
-    for (uint64_t blk = blockIdx.x; blk < nblk; blk += gdim) {
-        const uint64_t g0 = blk * 256, gid = g0 + threadIdx.x;
-        const uint64_t g = gid < a.total ? gid : a.total - 1;
-        const uint64_t bt = g >> log_d, i = g & ((1ull << log_d) - 1);
-        const C2* src = static_cast<const C2*>(a.in) + bt * a.in_bstride + i;
-        C2 v[V];
-#pragma unroll
-        for (int m = 0; m < V; m++) {
-            if constexpr (SW & 1) v[m] = sw_in<SW>(src[(uint64_t)m << log_d]);
-            else v[m] = src[(uint64_t)m << log_d];
-        }
-        tree_levels<T, L>(v, a.tw, i, log_d, 0, 0, 0, 0, V);
-        __syncthreads();  // the previous round's reads of `stage` are done
-#pragma unroll
-        for (int m = 0; m < V; m++) stage[tree_wil_pad(threadIdx.x * V + m)] = v[m];
-        __syncthreads();
-        const uint64_t b0 = g0 >> log_d, i0 = g0 & ((1ull << log_d) - 1);
-        C2* dst = static_cast<C2*>(a.out) + b0 * a.out_bstride + (i0 << L);
-        const uint64_t nvalid = (a.total - g0 < 256 ? a.total - g0 : 256) * V;
-#pragma unroll
-        for (int k = 0; k < V; k++) {
-            const uint32_t idx = (uint32_t)k * 256 + threadIdx.x;
-            if (idx < nvalid) dst[idx] = stage[tree_wil_pad(idx)];
-        }
-    }
+    PIFFT_TREE_WIL_BODY(0);
 }
 // inverse plans (SW 1: it reads the caller's input; its output feeds the passes)
 template <typename T, int L, int SW>
 __global__ __launch_bounds__(256) void k_tree_wil_sw(TreeArgs a) {
     static_assert(SW == 1, "k_tree_wil never writes the caller's output");
-    tree_wil_body<T, L, SW>(a, gridDim.x);
+    PIFFT_TREE_WIL_BODY(SW);
 }
 
 // ---------------------------------------------------------------------------
 // slice-major -> natural order: out[bt N + bitrev_P(q) + P k] = in[bt N + q M + k]
 // ---------------------------------------------------------------------------
+#define PIFFT_INTERLEAVE_BODY(SW)                                                                                     \
+    const uint64_t n = 1ull << log_n;                                                                                 \
+    for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;                                 \
+         gid += (uint64_t)gridDim.x * blockDim.x) {                                                                   \
+        const uint64_t bt = gid >> log_n, o = gid & (n - 1);                                                          \
+        const uint64_t k = o >> log_p;                                                                                \
+        const uint32_t rr = (uint32_t)(o & ((1ull << log_p) - 1));                                                    \
+        const uint32_t q = log_p ? (__builtin_bitreverse32(rr) >> (32 - log_p)) : 0u;                                 \
+        if constexpr ((SW) & 2) out[gid] = sw_out<(SW)>(in[bt * n + ((uint64_t)q << (log_n - log_p)) + k]);           \
+        else out[gid] = in[bt * n + ((uint64_t)q << (log_n - log_p)) + k];                                            \
+    }
 template <typename T>
 __global__ __launch_bounds__(256) void k_interleave(const cx<T>* __restrict__ in,
                                                     cx<T>* __restrict__ out, uint64_t total,
                                                     uint32_t log_n, uint32_t log_p) {
-    const uint64_t n = 1ull << log_n;
-    for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
-         gid += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t bt = gid >> log_n, o = gid & (n - 1);
-        const uint64_t k = o >> log_p;
-        const uint32_t rr = (uint32_t)(o & ((1ull << log_p) - 1));
-        const uint32_t q = log_p ? (__builtin_bitreverse32(rr) >> (32 - log_p)) : 0u;
-        out[gid] = in[bt * n + ((uint64_t)q << (log_n - log_p)) + k];
-    }
-}
-// The swapping twin's body (inverse plans): k_interleave's own statements with SW's
-// swaps.  The forward kernel above keeps its text: compiled as a call of this
-// body at SW = 0 it came out as different (equivalent) code -- the launch
-// geometry reads and the kernel-argument loads are lowered differently behind
-// a __device__ function -- and the forward code objects must not move.  Keep
-// the two in step.
-template <typename T, int SW>
-__device__ __forceinline__ void interleave_body(const cx<T>* __restrict__ in, cx<T>* __restrict__ out, uint64_t total,
-                                                uint32_t log_n, uint32_t log_p, const uint32_t bdim,
-                                                const uint32_t gdim) {
-    const uint64_t n = 1ull << log_n;
-    for (uint64_t gid = (uint64_t)blockIdx.x * bdim + threadIdx.x; gid < total;
-         gid += (uint64_t)gdim * bdim) {
-        const uint64_t bt = gid >> log_n, o = gid & (n - 1);
-        const uint64_t k = o >> log_p;
-        const uint32_t rr = (uint32_t)(o & ((1ull << log_p) - 1));
-        const uint32_t q = log_p ? (__builtin_bitreverse32(rr) >> (32 - log_p)) : 0u;
-        if constexpr (SW & 2) out[gid] = sw_out<SW>(in[bt * n + ((uint64_t)q << (log_n - log_p)) + k]);
-        else out[gid] = in[bt * n + ((uint64_t)q << (log_n - log_p)) + k];
-    }
+    PIFFT_INTERLEAVE_BODY(0);
 }
 // inverse plans: the interleave launch writes the caller's output (SW 2)
 template <typename T, int SW>
@@ -1860,7 +1778,7 @@ __global__ __launch_bounds__(256) void k_interleave_sw(const cx<T>* __restrict__
                                                        cx<T>* __restrict__ out, uint64_t total,
                                                        uint32_t log_n, uint32_t log_p) {
     static_assert(SW == 2, "k_interleave never reads the caller's input");
-    interleave_body<T, SW>(in, out, total, log_n, log_p, blockDim.x, gridDim.x);
+    PIFFT_INTERLEAVE_BODY(SW);
 }
 
 // The same through an LDS tile of all P slices x K = 2048/P consecutive k
@@ -1872,81 +1790,45 @@ __global__ __launch_bounds__(256) void k_interleave_sw(const cx<T>* __restrict__
 // P = 256 0.34 -> 0.09 ms, fp32 2^24 P = 8 0.053 -> 0.044 ms; for fp64 P <= 16
 // k_interleave is as fast or faster (2^28 P = 8: 1.52 vs 1.62 ms).
 constexpr int IL_TILE = 2048;
+// K = 2048 / P = 2^log_k; e0: the first output of a tile, o: the natural
+// position within it; the first barrier: the previous tile's reads are done.
+#define PIFFT_INTERLEAVE_TILE_BODY(SW)                                                                                \
+    __shared__ cx<T> tile[IL_TILE + IL_TILE / 16];                                                                    \
+    const uint32_t log_k = 11 - log_p;                                                                                \
+    const uint32_t log_m = log_n - log_p;                                                                             \
+    const uint64_t ntiles = total >> 11;                                                                              \
+    const uint32_t P = 1u << log_p;                                                                                   \
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {                                                       \
+        const uint64_t e0 = t << 11;                                                                                  \
+        const uint64_t bt = e0 >> log_n, k0 = (e0 & ((1ull << log_n) - 1)) >> log_p;                                  \
+        const cx<T>* src = in + (bt << log_n) + k0;                                                                   \
+        __syncthreads();                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < IL_TILE / 256; i++) {                                                   \
+            const uint32_t e = threadIdx.x + i * 256;                                                                 \
+            const uint32_t q = e >> log_k, k = e & ((1u << log_k) - 1);                                               \
+            const uint32_t r = log_p ? (__builtin_bitreverse32(q) >> (32 - log_p)) : 0u;                              \
+            const uint32_t o = (k << log_p) + r;                                                                      \
+            tile[o + (o >> 4)] = src[((uint64_t)q << log_m) + k];                                                     \
+        }                                                                                                             \
+        __syncthreads();                                                                                              \
+        cx<T>* dst = out + e0;                                                                                        \
+        _Pragma("unroll") for (int i = 0; i < IL_TILE / 256; i++) {                                                   \
+            const uint32_t o = threadIdx.x + i * 256;                                                                 \
+            if constexpr ((SW) & 2) dst[o] = sw_out<(SW)>(tile[o + (o >> 4)]);                                        \
+            else dst[o] = tile[o + (o >> 4)];                                                                         \
+        }                                                                                                             \
+        (void)P;                                                                                                      \
+    }
 template <typename T>
 __global__ __launch_bounds__(256) void k_interleave_tile(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
                                                          uint64_t total, uint32_t log_n, uint32_t log_p) {
-    __shared__ cx<T> tile[IL_TILE + IL_TILE / 16];
-    const uint32_t log_k = 11 - log_p;  // K = 2048 / P
-    const uint32_t log_m = log_n - log_p;
-    const uint64_t ntiles = total >> 11;
-    const uint32_t P = 1u << log_p;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t e0 = t << 11;  // first output of the tile
-        const uint64_t bt = e0 >> log_n, k0 = (e0 & ((1ull << log_n) - 1)) >> log_p;
-        const cx<T>* src = in + (bt << log_n) + k0;
-        __syncthreads();  // the previous tile's reads are done
-#pragma unroll
-        for (int i = 0; i < IL_TILE / 256; i++) {
-            const uint32_t e = threadIdx.x + i * 256;
-            const uint32_t q = e >> log_k, k = e & ((1u << log_k) - 1);
-            const uint32_t r = log_p ? (__builtin_bitreverse32(q) >> (32 - log_p)) : 0u;
-            const uint32_t o = (k << log_p) + r;  // natural position within the tile
-            tile[o + (o >> 4)] = src[((uint64_t)q << log_m) + k];
-        }
-        __syncthreads();
-        cx<T>* dst = out + e0;
-#pragma unroll
-        for (int i = 0; i < IL_TILE / 256; i++) {
-            const uint32_t o = threadIdx.x + i * 256;
-            dst[o] = tile[o + (o >> 4)];
-        }
-        (void)P;
-    }
-}
-// The swapping twin's body (inverse plans): k_interleave_tile's own statements with SW's
-// swaps.  The forward kernel above keeps its text: compiled as a call of this
-// body at SW = 0 it came out as different (equivalent) code -- the launch
-// geometry reads and the kernel-argument loads are lowered differently behind
-// a __device__ function -- and the forward code objects must not move.  Keep
-// the two in step.
-template <typename T, int SW>
-__device__ __forceinline__ void interleave_tile_body(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
-                                                     uint64_t total, uint32_t log_n, uint32_t log_p,
-                                                     const uint32_t gdim) {
-    __shared__ cx<T> tile[IL_TILE + IL_TILE / 16];
-    const uint32_t log_k = 11 - log_p;  // K = 2048 / P
-    const uint32_t log_m = log_n - log_p;
-    const uint64_t ntiles = total >> 11;
-    const uint32_t P = 1u << log_p;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gdim) {
-        const uint64_t e0 = t << 11;  // first output of the tile
-        const uint64_t bt = e0 >> log_n, k0 = (e0 & ((1ull << log_n) - 1)) >> log_p;
-        const cx<T>* src = in + (bt << log_n) + k0;
-        __syncthreads();  // the previous tile's reads are done
-#pragma unroll
-        for (int i = 0; i < IL_TILE / 256; i++) {
-            const uint32_t e = threadIdx.x + i * 256;
-            const uint32_t q = e >> log_k, k = e & ((1u << log_k) - 1);
-            const uint32_t r = log_p ? (__builtin_bitreverse32(q) >> (32 - log_p)) : 0u;
-            const uint32_t o = (k << log_p) + r;  // natural position within the tile
-            tile[o + (o >> 4)] = src[((uint64_t)q << log_m) + k];
-        }
-        __syncthreads();
-        cx<T>* dst = out + e0;
-#pragma unroll
-        for (int i = 0; i < IL_TILE / 256; i++) {
-            const uint32_t o = threadIdx.x + i * 256;
-            if constexpr (SW & 2) dst[o] = sw_out<SW>(tile[o + (o >> 4)]);
-            else dst[o] = tile[o + (o >> 4)];
-        }
-        (void)P;
-    }
+    PIFFT_INTERLEAVE_TILE_BODY(0);
 }
 template <typename T, int SW>
 __global__ __launch_bounds__(256) void k_interleave_tile_sw(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
                                                             uint64_t total, uint32_t log_n, uint32_t log_p) {
     static_assert(SW == 2, "k_interleave_tile never reads the caller's input");
-    interleave_tile_body<T, SW>(in, out, total, log_n, log_p, gridDim.x);
+    PIFFT_INTERLEAVE_TILE_BODY(SW);
 }
 
 // ---------------------------------------------------------------------------

@@ -120,6 +120,10 @@ SHAPES_BY_PREC = [
                                "f32": ([T, T, PS, PS, IL], [0, 0, 1, 2, 0])}),  # fp32: ends in an interleave launch
     ((23, 2, 0, 2, NAT, 1), {"f64": ([TP, PS, PS], [11, 10, 10])}),
     ((21, 2, 0, 2, NAT, 3), {"f32": ([TP, PS, PS], [11, 10, 10])}),
+    # the tiled interleave launch's twin (fp64 from P = 32) and, fp64 P = 16, the 4-level
+    # worker-interleaved tree launch's
+    ((16, 32, 0, 32, NAT, 1), {"f64": ([T, T, PS, IL], [0, 0, 0, 0]), "f32": ([T, T, PS, IL], [0, 0, 0, 0])}),
+    ((18, 16, 0, 16, NAT, 1), {"f64": ([T, PS, PS], [0, 10, 10]), "f32": ([TP, PS], [11, 10])}),
 ]
 CASES = [(suf, sh, k, m) for sh, k, m in SHAPES for suf in ("f64", "f32")] + \
         [(suf, sh, k, m) for sh, by in SHAPES_BY_PREC for suf, (k, m) in by.items()]

@@ -36,6 +36,11 @@ SHAPES = [
     ("C3 fp32 4096 x 4096", 12, 1, 0, 1, 4096, 32),
     ("C4 fp64 2^28 P=1", 28, 1, 0, 1, 1, 64),
     ("C4 fp32 2^28 P=1", 28, 1, 0, 1, 1, 32),
+    # the tree and interleave launches' twins: a tree twin (+ the plain interleave twin), a
+    # worker-interleaved tree twin, two tree twins + the tiled interleave twin
+    ("tree twin fp64 2^15 P=16", 15, 16, 0, 16, 1, 64),
+    ("worker-interleaved tree twin fp64 2^23 P=16", 23, 16, 0, 16, 1, 64),
+    ("tiled interleave twin fp64 2^16 P=32", 16, 32, 0, 32, 1, 64),
 ]
 
 
