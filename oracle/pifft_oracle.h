@@ -46,6 +46,10 @@ void oracle_generate_f64(oracle_cx_f64* x, uint64_t count, uint64_t n, uint64_t 
 
 int oracle_kat_f32(uint32_t P);
 
+/* fft_hp.c: the long-double radix-2 FFT the oracle's and the kernels' errors
+ * are measured against; in place on n (re, im) long-double pairs. */
+int oracle_fft_hp(long double* buf, uint64_t n, uint32_t levels, int reorder);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ def lib() -> ctypes.CDLL:
         L.oracle_splitmix64.restype = u64
         L.oracle_kat_f32.argtypes = [u32]
         L.oracle_kat_f32.restype = ctypes.c_int
+        L.oracle_fft_hp.argtypes = [vp, u64, u32, ctypes.c_int]
+        L.oracle_fft_hp.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -109,6 +111,36 @@ def tree_segment(x: np.ndarray, P: int, q: int) -> np.ndarray:
     if rc:
         raise RuntimeError("oracle_tree_segment failed")
     return seg
+
+
+def _hp(x: np.ndarray, levels: int, reorder: bool) -> np.ndarray:
+    # np.clongdouble must be the C long double pair fft_hp.c works on: the x87
+    # 80-bit format (64-bit significand), as on x86-64.  Elsewhere long double
+    # is double or a double-double, and the yardstick would be no yardstick.
+    if np.finfo(np.longdouble).nmant < 63 or np.dtype(np.clongdouble).itemsize != 2 * ctypes.sizeof(ctypes.c_longdouble):
+        raise RuntimeError("fft_hp needs an 80-bit long double (np.longdouble has a %d-bit mantissa here)"
+                           % np.finfo(np.longdouble).nmant)
+    _suf(x.dtype)
+    if x.ndim != 1:
+        raise ValueError("fft_hp takes one transform")
+    buf = np.ascontiguousarray(x).astype(np.clongdouble)  # exact widening
+    rc = lib().oracle_fft_hp(buf.ctypes.data, buf.shape[0], levels, int(reorder))
+    if rc:
+        raise RuntimeError(f"oracle_fft_hp failed rc={rc}")
+    return buf
+
+
+def fft_hp(x: np.ndarray) -> np.ndarray:
+    """The DFT of x (complex64 / complex128, widened exactly) by a radix-2 FFT
+    in long double (fft_hp.c), natural order: the yardstick the oracle's and
+    the kernels' errors are measured against."""
+    return _hp(x, 0xFFFFFFFF, True)
+
+
+def tree_hp(x: np.ndarray, P: int) -> np.ndarray:
+    """fft_hp's first log2 P DIF levels: worker q's segment behind the tree
+    stage (tree_segment(x, P, q) in exact arithmetic) at [q N/P, (q+1) N/P)."""
+    return _hp(x, P.bit_length() - 1, False)
 
 
 def bit_reverse(x: int, m: int) -> int:
