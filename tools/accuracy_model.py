@@ -16,6 +16,10 @@ sigma_k / sigma_o, the tail factor h (how much further the maximum over N bins
 of the kernel's scale-mixture errors sits above its rms than that of N
 equal-variance Gaussians), r h, and 1.3 r h (1.3: the same allowance for the
 spread of a maximum that the factor 4 carries).  numpy only.
+
+worst_bin_bound(c_o, passes, log2 N, bins) is that last figure as a function,
+the tail taken over `bins` bins (default N): tests/test_gpu_instances.py puts
+several hundred cases under one bound and takes bins = N times their number.
 """
 import math
 import os
@@ -92,6 +96,32 @@ def hermitian():
                   f"  | generic input, whole error {tot:.3f}")
 
 
+SPREAD = 1.3  # the allowance for the spread of a maximum that the factor 4 carries
+
+
+def model(co, passes, logn, bins=None):
+    """(sigma_o, sigma_k, r, h) of a plan of `passes` passes at N = 2^logn,
+    the oracle's constant co: the kernel's worst error taken over `bins` bins
+    (default N: one transform), the oracle's over its own N.  More bins than
+    N: a bound shared by several cases, the largest of whose ratios is held
+    to it (tests/test_gpu_instances.py: bins = N times their number)."""
+    c2, coh2 = chain_variance()
+    n = 2.0 ** logn
+    so2 = co ** 2 * logn
+    sk2 = so2 + (passes - 1) * c2
+    r = np.sqrt(sk2 / so2)
+    # only the LAST pass's chain stays coherent over final bins: earlier
+    # passes' lines are mixed by the passes behind them
+    h = tail(n if bins is None else float(bins), sk2 - coh2, coh2) / np.sqrt(sk2 * np.log(n))
+    return np.sqrt(so2), np.sqrt(sk2), r, h
+
+
+def worst_bin_bound(co, passes, logn, bins=None):
+    """The worst-bin bound, in units of the oracle's worst bin: 1.3 r h."""
+    _, _, r, h = model(co, passes, logn, bins)
+    return float(SPREAD * r * h)
+
+
 def main():
     c2, coh2 = chain_variance()
     print(f"sigma_delta {2 * RHO:.2f} u; chain term per inter-pass twiddle {np.sqrt(c2):.2f} u "
@@ -101,15 +131,9 @@ def main():
     for name, co in (("fp32", 0.66), ("fp64", 1.45), ("C2R fp32", 0.65), ("C2R fp64", 0.69)):
         for p in (2, 3):
             for logn in (14, 16, 18, 20, 21, 22):
-                n = 2.0 ** logn
-                so2 = co ** 2 * logn
-                sk2 = so2 + (p - 1) * c2
-                r = np.sqrt(sk2 / so2)
-                # only the LAST pass's chain stays coherent over final bins: earlier
-                # passes' lines are mixed by the passes behind them
-                h = tail(n, sk2 - coh2, coh2) / np.sqrt(sk2 * np.log(n))
-                print(f"{name} p={p} 2^{logn}: sigma_o {np.sqrt(so2):.2f} u  sigma_k {np.sqrt(sk2):.2f} u  "
-                      f"r {r:.2f}  h {h:.2f}  r h {r * h:.2f}  1.3 r h {1.3 * r * h:.2f}")
+                so, sk, r, h = model(co, p, logn)
+                print(f"{name} p={p} 2^{logn}: sigma_o {so:.2f} u  sigma_k {sk:.2f} u  "
+                      f"r {r:.2f}  h {h:.2f}  r h {r * h:.2f}  1.3 r h {SPREAD * r * h:.2f}")
 
 
 if __name__ == "__main__":
