@@ -90,3 +90,32 @@ def test_policy_alone_chooses_the_librarys_plans(exe):
         assert (got["fused"] != "0") == ("tree+pass" in d["launch_kind"]), shp
         plans += 1
     assert plans > 300 and refused > 0  # (the random shapes include some no instance serves)
+
+
+def test_every_default_plan_of_the_domain_is_the_recorded_one(exe):
+    """Every shape of the planner's domain (tools/instance_sweep.py shapes, N =
+    2^1 .. 2^32) under the default planner: the harness's output for each N
+    has the SHA-256 recorded in tests/golden/planner_domain_sha256.txt ("log_n
+    digest" per line, made from the header before its rules were split into
+    functions).  Any change of any default plan, layout, tree table or refusal
+    shows here, not only a change of the instance set."""
+    import hashlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    import instance_sweep
+    with open(os.path.join(HERE, "golden", "planner_domain_sha256.txt")) as f:
+        want = {int(ln.split()[0]): ln.split()[1] for ln in f if ln.strip()}
+    assert sorted(want) == list(range(1, 33))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("PIFFT_")}  # the default planner
+
+    def digest(log_n):
+        text = "".join("%d %d %d %d %d %d %d\n" % s for s in instance_sweep.shapes(log_n))
+        out = subprocess.run([exe] + LISTS, input=text.encode(), check=True, capture_output=True, env=env).stdout
+        assert out.count(b"\n") == text.count("\n"), log_n
+        return hashlib.sha256(out).hexdigest()
+
+    with ThreadPoolExecutor(max_workers=4) as ex:  # (four harness processes at a time)
+        got = dict(zip(want, ex.map(digest, want)))
+    changed = [log_n for log_n in want if got[log_n] != want[log_n]]
+    assert not changed, (f"default plans changed at N = 2^{changed}: compare tools/instance_sweep.py --plans FILE.json "
+                         "of this build and of the previous one with --compare")

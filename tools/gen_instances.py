@@ -108,7 +108,7 @@ for R in (256, 512):
 # MODE 11 = 3 | 8: the tree of all P workers fused into the first
 # worker-interleaved pass (round 5).  A tile is J adjacent line indices x the P
 # workers (C = J P lines) at the 8192-value tile (R = 8192 / C), P = 2..16.
-# The planner's J (choose_plan, pifft_planner.h): fp64 J = 8 (P <= 8, and P = 16 from
+# The planner's J (wil_fuse_tile, pifft_planner.h): fp64 J = 8 (P <= 8, and P = 16 from
 # 256 MiB); fp32 J = 8 up to 32 MiB and 16 up to 1 GiB; J = 4 (4096-value tile
 # below 256 workgroups, or where J = 8 would split the remainder) and J = 2
 # (fp64 P = 16, 32-64 MiB) as refinements below; other J only under

@@ -27,7 +27,7 @@ two passes; a multi-pass case has N >= 2^14 (the accuracy bounds' derivation
 holds from there); every pass's line count is a multiple of its lines per
 workgroup C, and C does not exceed the lines of one transform (times P for the
 worker-interleaved layout; a single pass's lines are whole transforms, so
-there C is capped by their number, as pick_lines does).
+there C is capped by their number, as single_pass asks of pick_lines).
 
 The search: every default plan of the shape grid first; then, per instance or
 twin still open, the shapes its descriptor allows under the subsets of the
@@ -140,7 +140,7 @@ def preflight(case: Case, passes: list, wil: bool):
             return f"R = {R} does not divide M = {m}"
         if (ntrans * per) % C:
             return f"{ntrans * per} lines are no multiple of C = {C}"
-        # a single pass's lines are whole transforms: pick_lines caps C by their number
+        # a single pass's lines are whole transforms: pick_lines caps C by their number (single_pass)
         cap = ntrans if len(passes) == 1 and not wil else per * case.P if wil else per
         if C > cap:
             return f"C = {C} exceeds the {cap} lines it may span"
