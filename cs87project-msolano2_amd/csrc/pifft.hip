@@ -82,10 +82,14 @@ constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
 
 
 // 1-D grid for a grid-stride kernel of `total` items at 256 threads/block:
-// capped so the launch's work-item count stays far below 2^32
+// capped so the launch's work-item count stays far below 2^32.
+// PIFFT_STRIDE_GRID_MAX (tuning, tests): a smaller cap, so that a small launch
+// makes second and later trips of its grid-stride loop (tests/test_gpu_aux.py)
+constexpr int kStrideGridMax = 262144;
 unsigned stride_grid(uint64_t total) {
+    const uint64_t cap = (uint64_t)std::min(std::max(env_int("PIFFT_STRIDE_GRID_MAX", kStrideGridMax), 1), kStrideGridMax);
     const uint64_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks < 262144 ? (blocks ? blocks : 1) : 262144);
+    return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
 }
 uint32_t bitrev(uint32_t x, int m) { return m ? (__builtin_bitreverse32(x) >> (32 - m)) : 0u; }
 
@@ -184,28 +188,68 @@ const TwinKernel* find_twin(const PassKernel& k, int sw) {
     return nullptr;
 }
 
+// The registry of the auxiliary kernels -- every kernel that is not a k_pass
+// instance: the forward kernels (sw 0) and their swapping twins (inverse
+// plans).  The one place this file names them: assemble_steps, interleave_fn,
+// add_real_step, make_inverse and pifft_generate_device take their kernels
+// from here (find_aux), so none can be launched without being listed, and
+// pifft_aux_count / pifft_aux_desc / pifft_plan_dry_run_aux describe exactly
+// what can be launched (tests/test_aux_cases.py, tests/test_gpu_aux.py).
+struct AuxKernel {
+    int family, prec, L, sw;  // PIFFT_AUX_*; 32 / 64; tree levels (0: the family has none); 0 or the twin's swaps
+    const void* fn;
+};
+#define PIFFT_AUX_TREE_ROWS(T, PREC, L)                                                            \
+    {PIFFT_AUX_TREE, PREC, L, 0, (const void*)&k_tree<T, L>},                                      \
+        {PIFFT_AUX_TREE, PREC, L, 1, (const void*)&k_tree_sw<T, L, 1>},                            \
+        {PIFFT_AUX_TREE, PREC, L, 2, (const void*)&k_tree_sw<T, L, 2>},                            \
+        {PIFFT_AUX_TREE, PREC, L, 3, (const void*)&k_tree_sw<T, L, 3>},                            \
+        {PIFFT_AUX_TREE_WIL, PREC, L, 0, (const void*)&k_tree_wil<T, L>},                          \
+        {PIFFT_AUX_TREE_WIL, PREC, L, 1, (const void*)&k_tree_wil_sw<T, L, 1>}
+#define PIFFT_AUX_INTERLEAVE_ROWS(FAMILY, K, T, PREC) \
+    {FAMILY, PREC, 0, 0, (const void*)&K<T>}, {FAMILY, PREC, 0, 2, (const void*)&K##_sw<T, 2>}
+const AuxKernel kAux[] = {
+    PIFFT_AUX_TREE_ROWS(double, 64, 1), PIFFT_AUX_TREE_ROWS(double, 64, 2), PIFFT_AUX_TREE_ROWS(double, 64, 3),
+    PIFFT_AUX_TREE_ROWS(double, 64, 4), PIFFT_AUX_TREE_ROWS(float, 32, 1),  PIFFT_AUX_TREE_ROWS(float, 32, 2),
+    PIFFT_AUX_TREE_ROWS(float, 32, 3),  PIFFT_AUX_TREE_ROWS(float, 32, 4),
+    PIFFT_AUX_INTERLEAVE_ROWS(PIFFT_AUX_INTERLEAVE, k_interleave, double, 64),
+    PIFFT_AUX_INTERLEAVE_ROWS(PIFFT_AUX_INTERLEAVE, k_interleave, float, 32),
+    PIFFT_AUX_INTERLEAVE_ROWS(PIFFT_AUX_INTERLEAVE_TILE, k_interleave_tile, double, 64),
+    PIFFT_AUX_INTERLEAVE_ROWS(PIFFT_AUX_INTERLEAVE_TILE, k_interleave_tile, float, 32),
+    {PIFFT_AUX_C2R, 64, 0, 0, (const void*)&k_c2r_pre<double>},
+    {PIFFT_AUX_R2C, 64, 0, 0, (const void*)&k_r2c_post<double>},
+    {PIFFT_AUX_C2R, 32, 0, 0, (const void*)&k_c2r_pre<float>},
+    {PIFFT_AUX_R2C, 32, 0, 0, (const void*)&k_r2c_post<float>},
+    {PIFFT_AUX_GENERATE, 64, 0, 0, (const void*)&k_generate<double>},
+    {PIFFT_AUX_GENERATE, 32, 0, 0, (const void*)&k_generate<float>},
+};
+#undef PIFFT_AUX_TREE_ROWS
+#undef PIFFT_AUX_INTERLEAVE_ROWS
+constexpr int kAuxCount = (int)(sizeof kAux / sizeof kAux[0]);
+
+const AuxKernel* find_aux(int family, int prec, int L, int sw) {
+    for (const AuxKernel& a : kAux)
+        if (a.family == family && a.prec == prec && a.L == L && a.sw == sw) return &a;
+    return nullptr;
+}
+// a forward kernel a plan cannot do without (every (family, precision, L) it asks for is listed above)
+const void* aux_fn(int family, int prec, int L = 0) {
+    const AuxKernel* a = find_aux(family, prec, L, 0);
+    return a ? a->fn : nullptr;
+}
+// the registry index of a launch's kernel, or -1 (a k_pass instance or twin)
+int aux_index(const void* fn) {
+    for (int i = 0; i < kAuxCount; i++)
+        if (kAux[i].fn == fn) return i;
+    return -1;
+}
+
 // the twins of the tree and interleave kernels: (forward kernel, sw) -> twin
 const void* find_aux_twin(const void* fn, int sw) {
-    struct Aux {
-        const void *fwd; int sw; const void *twin;
-    };
-#define PIFFT_TREE_TWINS(T, L)                                                                    \
-    {(const void*)&k_tree<T, L>, 1, (const void*)&k_tree_sw<T, L, 1>},                            \
-        {(const void*)&k_tree<T, L>, 2, (const void*)&k_tree_sw<T, L, 2>},                        \
-        {(const void*)&k_tree<T, L>, 3, (const void*)&k_tree_sw<T, L, 3>},                        \
-        {(const void*)&k_tree_wil<T, L>, 1, (const void*)&k_tree_wil_sw<T, L, 1>}
-    static const Aux aux[] = {
-        PIFFT_TREE_TWINS(double, 1), PIFFT_TREE_TWINS(double, 2), PIFFT_TREE_TWINS(double, 3), PIFFT_TREE_TWINS(double, 4),
-        PIFFT_TREE_TWINS(float, 1),  PIFFT_TREE_TWINS(float, 2),  PIFFT_TREE_TWINS(float, 3),  PIFFT_TREE_TWINS(float, 4),
-        {(const void*)&k_interleave<double>, 2, (const void*)&k_interleave_sw<double, 2>},
-        {(const void*)&k_interleave<float>, 2, (const void*)&k_interleave_sw<float, 2>},
-        {(const void*)&k_interleave_tile<double>, 2, (const void*)&k_interleave_tile_sw<double, 2>},
-        {(const void*)&k_interleave_tile<float>, 2, (const void*)&k_interleave_tile_sw<float, 2>},
-    };
-#undef PIFFT_TREE_TWINS
-    for (const Aux& a : aux)
-        if (a.fwd == fn && a.sw == sw) return a.twin;
-    return nullptr;
+    const int i = aux_index(fn);
+    if (i < 0 || kAux[i].sw != 0) return nullptr;
+    const AuxKernel* t = find_aux(kAux[i].family, kAux[i].prec, kAux[i].L, sw);
+    return t ? t->fn : nullptr;
 }
 
 // ---------------------------------------------------------------------------
@@ -391,9 +435,7 @@ bool interleave_tiled(int prec, int lp, uint64_t n) {
     return lo > 0 && lp >= lo && lp <= 11 && n >= (uint64_t)IL_TILE;
 }
 const void* interleave_fn(int prec, int lp, uint64_t n) {
-    if (interleave_tiled(prec, lp, n))
-        return prec == 64 ? (const void*)&k_interleave_tile<double> : (const void*)&k_interleave_tile<float>;
-    return prec == 64 ? (const void*)&k_interleave<double> : (const void*)&k_interleave<float>;
+    return aux_fn(interleave_tiled(prec, lp, n) ? PIFFT_AUX_INTERLEAVE_TILE : PIFFT_AUX_INTERLEAVE, prec);
 }
 uint64_t interleave_threads(uint64_t total, int lp, int prec, uint64_t n) {
     return interleave_tiled(prec, lp, n) ? (total / IL_TILE) * 256 : total;
@@ -484,10 +526,6 @@ int assemble_steps(pifft_plan* p, const PlanChoice& ch, const TableLayout& tl) {
         std::vector<Step> e;
         // ceil(log2 P / 4) launches of up to 4 levels each; in place over
         // one position-space buffer between launches (see k_tree)
-        static const void* tk64[5] = {nullptr, (const void*)&k_tree<double, 1>, (const void*)&k_tree<double, 2>,
-                                      (const void*)&k_tree<double, 3>, (const void*)&k_tree<double, 4>};
-        static const void* tk32[5] = {nullptr, (const void*)&k_tree<float, 1>, (const void*)&k_tree<float, 2>,
-                                      (const void*)&k_tree<float, 3>, (const void*)&k_tree<float, 4>};
         const int nl = (p->lp + 3) / 4;
         // number of level-t blocks (P >> t workers each) holding a requested worker
         auto blocks_needed = [&](int t) -> uint64_t {
@@ -500,7 +538,7 @@ int assemble_steps(pifft_plan* p, const PlanChoice& ch, const TableLayout& tl) {
             const bool first = (l == 0), last = (l == nl - 1);
             Step s;
             s.kind = STEP_TREE;
-            s.fn = p->prec == 64 ? tk64[L] : tk32[L];
+            s.fn = aux_fn(PIFFT_AUX_TREE, p->prec, L);  // (1 <= L <= 4: the registry holds every one)
             s.src = first ? -1 : BUF_TA;  // -1: chain input
             s.dst = last ? -2 : BUF_TA;   // -2: chain output (slice-major)
             s.ta.tw = ttw;
@@ -530,12 +568,8 @@ int assemble_steps(pifft_plan* p, const PlanChoice& ch, const TableLayout& tl) {
             p->tree_only.push_back(t);
         }
         if (p->wil && p->lp <= 4) {  // one launch over all workers: the passes' interleaved layout
-            static const void* tw64[5] = {nullptr, (const void*)&k_tree_wil<double, 1>, (const void*)&k_tree_wil<double, 2>,
-                                          (const void*)&k_tree_wil<double, 3>, (const void*)&k_tree_wil<double, 4>};
-            static const void* tw32[5] = {nullptr, (const void*)&k_tree_wil<float, 1>, (const void*)&k_tree_wil<float, 2>,
-                                          (const void*)&k_tree_wil<float, 3>, (const void*)&k_tree_wil<float, 4>};
             Step& t = e.back();
-            t.fn = p->prec == 64 ? tw64[p->lp] : tw32[p->lp];
+            t.fn = aux_fn(PIFFT_AUX_TREE_WIL, p->prec, p->lp);
             tree_tables(t, true);
             t.ta.out_bstride = p->n;
             t.lds = (size_t)tree_wil_pad(256u << p->lp) * esz;
@@ -676,8 +710,7 @@ void add_real_step(pifft_plan* p, TableBuilder& tb, uint64_t n, bool c2r) {
     p->rtw_bytes = tb.size() - before;
     Step s;
     s.kind = c2r ? STEP_C2R_PRE : STEP_R2C_POST;
-    s.fn = p->prec == PIFFT_F64 ? (c2r ? (const void*)&k_c2r_pre<double> : (const void*)&k_r2c_post<double>)
-                                : (c2r ? (const void*)&k_c2r_pre<float> : (const void*)&k_r2c_post<float>);
+    s.fn = aux_fn(c2r ? PIFFT_AUX_C2R : PIFFT_AUX_R2C, p->prec);
     s.tab.lo = tw.lo;
     s.tab.hi = tw.hi;
     s.ra.tw_h = tw.h;
@@ -1306,6 +1339,47 @@ int pifft_plan_dry_run_instances(uint64_t n, uint32_t workers, uint32_t first, u
     return nl;
 }
 
+int pifft_aux_count(void) { return kAuxCount; }
+
+int pifft_aux_desc(int i, int32_t* desc) {
+    if (!desc) return fail("desc is NULL");
+    if (i < 0 || i >= kAuxCount) return fail("auxiliary kernel %d out of range", i);
+    const int32_t d[4] = {kAux[i].family, kAux[i].prec, kAux[i].L, kAux[i].sw};
+    memcpy(desc, d, sizeof d);
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// the dry-run plan's launches: registry index (-1: a k_pass launch) and grid size in blocks
+int describe_aux(pifft_plan* p, int32_t* ids, uint32_t* grids, int max_ids) {
+    const int nl = (int)p->steps.size();
+    for (int i = 0; i < nl && i < max_ids; i++) {
+        if (ids) ids[i] = (int32_t)aux_index(p->steps[(size_t)i].fn);
+        if (grids) grids[i] = p->steps[(size_t)i].grid.x;
+    }
+    release(p);
+    return nl;
+}
+}  // namespace
+
+extern "C" {
+
+int pifft_plan_dry_run_aux(uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch, int prec,
+                           int flags, int32_t* ids, uint32_t* grids, int max_ids) {
+    pifft_plan* p = nullptr;
+    if (create(&p, n, workers, first, count, batch, prec, -1, flags, true)) return -1;
+    return describe_aux(p, ids, grids, max_ids);
+}
+
+int pifft_plan_dry_run_aux_real(uint64_t n, uint32_t workers, uint32_t batch, int prec, int direction, int32_t* ids,
+                                uint32_t* grids, int max_ids) {
+    pifft_plan* p = nullptr;
+    if (create_real(&p, n, workers, batch, prec, -1, direction, true)) return -1;
+    return describe_aux(p, ids, grids, max_ids);
+}
+
 int pifft_plan_get_info(const pifft_plan* p, pifft_plan_info* info) {
     if (!p || !info) return fail("NULL argument");
     memset(info, 0, sizeof *info);
@@ -1764,14 +1838,10 @@ int pifft_generate_device(void* d_x, uint64_t count, uint64_t n, uint64_t seed, 
     if (!d_x) return fail("NULL buffer");
     if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("bad precision");
     if (count == 0) return 0;
-    const double scale = sqrt((double)n);
-    const dim3 blk(256), grd(stride_grid(count));
-    hipStream_t st = (hipStream_t)stream;
-    if (prec == PIFFT_F64)
-        hipLaunchKernelGGL(k_generate<double>, grd, blk, 0, st, (cx<double>*)d_x, count, scale, seed, first);
-    else
-        hipLaunchKernelGGL(k_generate<float>, grd, blk, 0, st, (cx<float>*)d_x, count, scale, seed, first);
-    HIPCHK(hipGetLastError());
+    double scale = sqrt((double)n);
+    void* args[] = {&d_x, &count, &scale, &seed, &first};
+    HIPCHK(hipLaunchKernel(aux_fn(PIFFT_AUX_GENERATE, prec), dim3(stride_grid(count)), dim3(256), args, 0,
+                           (hipStream_t)stream));
     return 0;
 }
 

@@ -4,7 +4,9 @@
 // any registry of instances (tests/native/planner_main.cpp).  Every measured
 // rule that decides a plan lives here, with the PIFFT_* knobs that steer it;
 // pifft.hip lays out the tables, assembles the launches (their own knobs: XCD
-// grouping, padded workspace rows, ...) and materialises them.
+// grouping, padded workspace rows, the grid of the grid-stride kernels --
+// PIFFT_TREE_GRID_DIV at the tree launches, PIFFT_STRIDE_GRID_MAX, the cap of
+// every such grid, 262144 workgroups by default --, ...) and materialises them.
 //
 // The includer defines find_pass (the registry lookup): pifft.hip over the
 // compiled instances, logging every instance found (pifft_instance_found).

@@ -112,6 +112,15 @@ _SIGS = {
     "pifft_plan_dry_run_instances": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                                     ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    "pifft_aux_count": (ctypes.c_int, []),
+    "pifft_aux_desc": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    "pifft_plan_dry_run_aux": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.c_int]),
+    "pifft_plan_dry_run_aux_real": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]),
 }
 SYMBOLS = tuple(_SIGS)
 
@@ -359,6 +368,70 @@ def dry_run_instances(n: int, workers: int = 1, batch: int = 1, prec: int = F64,
     if nl < 0:
         raise PifftError(f"pifft_plan_dry_run_instances: {last_error()}")
     return list(ids[:min(nl, MAX_LAUNCH_INFO)])
+
+
+AUX_TREE, AUX_TREE_WIL, AUX_INTERLEAVE, AUX_INTERLEAVE_TILE, AUX_R2C, AUX_C2R, AUX_GENERATE = range(7)  # PIFFT_AUX_*
+AUX_FIELDS = ("family", "prec", "L", "sw")
+_CTYPE = {F32: "float", F64: "double"}
+
+
+def aux_kernels() -> list:
+    """Every auxiliary kernel (all that is not k_pass) as (family, prec, L, SW),
+    in registry order (pifft_aux_desc)."""
+    out = []
+    d = (ctypes.c_int32 * 4)()
+    for i in range(lib().pifft_aux_count()):
+        _check(lib().pifft_aux_desc(i, d), "pifft_aux_desc")
+        out.append(tuple(d))
+    return out
+
+
+def aux_kernel_name(desc) -> str:
+    """The demangled kernel function of an auxiliary kernel's descriptor, as
+    Plan.kernel_name and profilers print it."""
+    family, prec, L, sw = desc
+    T = _CTYPE[prec]
+    if family in (AUX_TREE, AUX_TREE_WIL):
+        k = "k_tree" if family == AUX_TREE else "k_tree_wil"
+        return (f"void pifft::{k}_sw<{T}, {L}, {sw}>(pifft::TreeArgs)" if sw else
+                f"void pifft::{k}<{T}, {L}>(pifft::TreeArgs)")
+    if family in (AUX_INTERLEAVE, AUX_INTERLEAVE_TILE):
+        k = "k_interleave" if family == AUX_INTERLEAVE else "k_interleave_tile"
+        args = f"(pifft::cx<{T}> const*, pifft::cx<{T}>*, unsigned long, unsigned int, unsigned int)"
+        return f"void pifft::{k}_sw<{T}, {sw}>{args}" if sw else f"void pifft::{k}<{T}>{args}"
+    if family in (AUX_R2C, AUX_C2R):
+        return f"void pifft::{'k_r2c_post' if family == AUX_R2C else 'k_c2r_pre'}<{T}>(pifft::RealArgs)"
+    return f"void pifft::k_generate<{T}>(pifft::cx<{T}>*, unsigned long, double, unsigned long, unsigned long)"
+
+
+def _aux_result(nl: int, ids, grids, what: str) -> list:
+    if nl < 0:
+        raise PifftError(f"{what}: {last_error()}")
+    return list(zip(ids[:min(nl, MAX_LAUNCH_INFO)], grids[:min(nl, MAX_LAUNCH_INFO)]))
+
+
+def dry_run_aux(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, first: int = 0,
+                count: int | None = None, flags: int | None = None, inverse: bool = False) -> list:
+    """(registry index of the launch's auxiliary kernel, -1 for a k_pass
+    launch; grid size in workgroups) per launch of the plan pifft_plan_dry_run
+    describes (pifft_plan_dry_run_aux; flags as dry_run).  An inverse plan's
+    launches name their swapping twins."""
+    count = workers if count is None else count
+    if flags is None:
+        flags = OUT_NATURAL if count == workers else OUT_SLICES
+    if inverse:
+        flags |= INVERSE
+    ids, grids = (ctypes.c_int32 * MAX_LAUNCH_INFO)(), (ctypes.c_uint32 * MAX_LAUNCH_INFO)()
+    nl = lib().pifft_plan_dry_run_aux(n, workers, first, count, batch, prec, flags, ids, grids, MAX_LAUNCH_INFO)
+    return _aux_result(nl, ids, grids, "pifft_plan_dry_run_aux")
+
+
+def dry_run_aux_real(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, inverse: bool = False) -> list:
+    """dry_run_aux of the real plan pifft_plan_dry_run_real describes."""
+    ids, grids = (ctypes.c_int32 * MAX_LAUNCH_INFO)(), (ctypes.c_uint32 * MAX_LAUNCH_INFO)()
+    nl = lib().pifft_plan_dry_run_aux_real(n, workers, batch, prec, REAL_INVERSE if inverse else REAL_FORWARD, ids,
+                                           grids, MAX_LAUNCH_INFO)
+    return _aux_result(nl, ids, grids, "pifft_plan_dry_run_aux_real")
 
 
 def dry_run(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, first: int = 0,

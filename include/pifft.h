@@ -237,6 +237,39 @@ int pifft_instance_found(int i);
 int pifft_plan_dry_run_instances(uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch,
                                  int prec, int flags, int32_t* ids, int max_ids);
 
+/* The same for the auxiliary kernels -- every kernel that is not a k_pass
+ * instance or twin: k_tree, k_tree_wil, k_interleave, k_interleave_tile with
+ * their swapping twins (inverse plans), the real plans' fix-ups and the
+ * generator.  pifft_aux_desc writes {family, prec, L, SW} of kernel i
+ * (< pifft_aux_count()) to desc[0..3]: family one of PIFFT_AUX_*, prec 32 / 64,
+ * L the tree levels of a launch (1..4; 0 where the family has none), SW 0 for
+ * a forward kernel, else the twin's swaps (1 what it loads from d_in, 2 what it
+ * stores to d_out, 3 both).  The registry is the only place the library takes
+ * these kernels from, twins included.  pifft_plan_dry_run_aux plans as
+ * pifft_plan_dry_run does (pifft_plan_dry_run_aux_real: as
+ * pifft_plan_dry_run_real) and writes, for each launch i < min(launches,
+ * max_ids), the registry index of the kernel it runs -- the twin's own for an
+ * inverse plan; -1 for a k_pass launch -- to ids[i] and the launch's grid size
+ * in workgroups to grids[i] (either may be NULL); it returns the number of
+ * launches, or -1.  The auxiliary kernels walk their work in grid-stride loops
+ * over a grid capped at 262144 workgroups; under PIFFT_TUNING=1,
+ * PIFFT_STRIDE_GRID_MAX lowers that cap (plans, pifft_interleave_device,
+ * pifft_allgather, pifft_generate_device), so that a small launch makes
+ * second and later trips: tests/test_aux_cases.py, tests/test_gpu_aux.py. */
+#define PIFFT_AUX_TREE 0            /* k_tree<T, L>, k_tree_sw<T, L, SW>                   */
+#define PIFFT_AUX_TREE_WIL 1        /* k_tree_wil<T, L>, k_tree_wil_sw<T, L, 1>            */
+#define PIFFT_AUX_INTERLEAVE 2      /* k_interleave<T>, k_interleave_sw<T, 2>              */
+#define PIFFT_AUX_INTERLEAVE_TILE 3 /* k_interleave_tile<T>, k_interleave_tile_sw<T, 2>    */
+#define PIFFT_AUX_R2C 4             /* k_r2c_post<T>                                       */
+#define PIFFT_AUX_C2R 5             /* k_c2r_pre<T>                                        */
+#define PIFFT_AUX_GENERATE 6        /* k_generate<T> (pifft_generate_device; in no plan)   */
+int pifft_aux_count(void);
+int pifft_aux_desc(int i, int32_t* desc);
+int pifft_plan_dry_run_aux(uint64_t n, uint32_t workers, uint32_t first, uint32_t count, uint32_t batch, int prec,
+                           int flags, int32_t* ids, uint32_t* grids, int max_ids);
+int pifft_plan_dry_run_aux_real(uint64_t n, uint32_t workers, uint32_t batch, int prec, int direction, int32_t* ids,
+                                uint32_t* grids, int max_ids);
+
 /* The kernel function of launch `launch` (< info.num_launches), demangled as
  * profilers print it (e.g. "void pifft::k_pass<double, 512, 16, 2, 1, 0, 16>
  * (pifft::PassArgs)"), into buf (len bytes, truncated, NUL-terminated): maps a

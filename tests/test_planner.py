@@ -332,7 +332,8 @@ STRAY = {"PIFFT_ORDER": "1", "PIFFT_PASSES": "4", "PIFFT_RADIX_LOGS": "10,10,8",
          "PIFFT_SINGLE_TILE32": "8192", "PIFFT_LAST_VPT": "16", "PIFFT_FUSED_VPT": "16", "PIFFT_WIL_VPT": "16",
          "PIFFT_WIL_FUSE": "0", "PIFFT_WIL_FUSE_J": "16", "PIFFT_WIL_TREE_DIRECT": "1", "PIFFT_WIL_TREE_MIN_LOG": "0",
          "PIFFT_PERMLANE": "0", "PIFFT_FAULT": "broadcast",
-         "PIFFT_WIL_FUSE_TILE": "2048", "PIFFT_WIL_SINGLE": "0", "PIFFT_WIL_ONE_LAUNCH": "0"}
+         "PIFFT_WIL_FUSE_TILE": "2048", "PIFFT_WIL_SINGLE": "0", "PIFFT_WIL_ONE_LAUNCH": "0",
+         "PIFFT_STRIDE_GRID_MAX": "1"}
 
 
 @pytest.mark.parametrize("shape", [(1 << 28, 1, 1, F64, 0, 1, 0), (1 << 28, 1, 1, F32, 0, 1, 0),
@@ -345,11 +346,14 @@ def test_stray_tuning_variables_are_ignored(shape, monkeypatch):
     n, P, b, prec, first, count, flags = shape
     monkeypatch.delenv("PIFFT_TUNING")
     want = pifft.dry_run(n, P, b, prec, first=first, count=count, flags=flags)
+    grids = pifft.dry_run_aux(n, P, b, prec, first=first, count=count, flags=flags)  # (PIFFT_STRIDE_GRID_MAX)
     for k, v in STRAY.items():
         monkeypatch.setenv(k, v)
     assert pifft.dry_run(n, P, b, prec, first=first, count=count, flags=flags) == want
+    assert pifft.dry_run_aux(n, P, b, prec, first=first, count=count, flags=flags) == grids
     monkeypatch.setenv("PIFFT_TUNING", "0")
     assert pifft.dry_run(n, P, b, prec, first=first, count=count, flags=flags) == want
+    assert pifft.dry_run_aux(n, P, b, prec, first=first, count=count, flags=flags) == grids
     # ... and the same variables do take effect under PIFFT_TUNING=1
     monkeypatch.setenv("PIFFT_TUNING", "1")
     assert pifft.dry_run(n, P, b, prec, first=first, count=count, flags=flags) != want
