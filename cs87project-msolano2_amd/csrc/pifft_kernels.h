@@ -152,29 +152,31 @@ __device__ __forceinline__ void dft(cx<T>* v) {
 // selects non-temporal (nt) loads/stores for it -- a win when a pass streams
 // more than the 256 MiB Infinity Cache holds, a loss when the data would
 // otherwise stay resident there (measured).
-#ifndef PIFFT_NT_LOADS
-#define PIFFT_NT_LOADS 1  // build-time switches for A/B variants (tools/mkvariant.sh)
-#endif
-#ifndef PIFFT_NT_STORES
-#define PIFFT_NT_STORES 1
-#endif
+//
+// Build-time switches: two are left.  PIFFT_WG_CLOCK (compiled out by default)
+// builds the per-workgroup step clocks of tools/wg_clock.py, and
+// PIFFT_LDS_DEFAULT_ONLY lets tools/lds_model.hip bootstrap the LDS layout
+// generator without the layouts it generates.  The choices that six rounds of
+// A/B builds settled -- each with its reason and log where it is made below --
+// are plain constants now; fixing them left every gfx950 code object byte for
+// byte what it was (profiles/kernel_switches_code_objects.txt).  A new A/B is
+// built with tools/mkvariant.sh: KERNELS_H=<edited header>, or EXTRA= for
+// these two switches.
+//
 // NTS (k_pass template argument): 0 plain; 1 nt loads and stores
 constexpr bool nt_loads(int nt) { return nt == 1; }
 constexpr bool nt_stores(int nt) { return nt == 1; }
-// PIFFT_VEC_NT: a complex value moves as ONE 8- or 16-byte vector access
-// (1: both precisions, 2: fp32 only, 0: two scalar nt accesses, which the
-// compiler merges -- for fp32 into loads that waited on each other).
-// Measured on MI355X (profiles/r03_ab_kernel_forms.log): fp32 2^28 3.23 ->
-// 3.04 ms with 2 (the same with 1); fp64 2^28 within the box's +-2 % spread
-// either way, so fp64 keeps its round-2 code (2).
-#ifndef PIFFT_VEC_NT
-#define PIFFT_VEC_NT 2
-#endif
+// vec_nt: a complex nt value moves as ONE 8-byte vector access for fp32, as
+// two scalar nt accesses for fp64 (which the compiler merges -- for fp32 into
+// loads that waited on each other).  Measured on MI355X
+// (profiles/r03_ab_kernel_forms.log): fp32 2^28 3.23 -> 3.04 ms with the
+// vector form; fp64 2^28 within the box's +-2 % spread either way, so fp64
+// keeps its round-2 code.
 template <typename T>
 using vec2_t = T __attribute__((ext_vector_type(2)));
 template <typename T>
 constexpr bool vec_nt() {
-    return PIFFT_VEC_NT == 1 || (PIFFT_VEC_NT == 2 && sizeof(T) == 4);
+    return sizeof(T) == 4;
 }
 // Inverse transforms (PIFFT_INVERSE): IDFT(x) = swap(DFT(swap(x))) with
 // swap(a + bi) = b + ai, so an inverse plan is the forward plan whose one
@@ -203,10 +205,10 @@ __device__ __forceinline__ cx<T> ld_stream(const cx<T>* p) {
     if constexpr (SW & 1) {
         const cx<T> r = ld_stream<NTS>(p);
         return cx<T>{r.im, r.re};
-    } else if constexpr (NTS && PIFFT_NT_LOADS && vec_nt<T>()) {
+    } else if constexpr (NTS && vec_nt<T>()) {
         const vec2_t<T> r = __builtin_nontemporal_load(reinterpret_cast<const vec2_t<T>*>(p));
         return cx<T>{r.x, r.y};
-    } else if constexpr (NTS && PIFFT_NT_LOADS) {
+    } else if constexpr (NTS) {
         cx<T> r;
         r.re = __builtin_nontemporal_load(&p->re);
         r.im = __builtin_nontemporal_load(&p->im);
@@ -219,27 +221,24 @@ template <bool NTS, int SW = 0, typename T>
 __device__ __forceinline__ void st_stream(cx<T>* p, cx<T> v) {
     if constexpr (SW & 2) {
         st_stream<NTS>(p, cx<T>{v.im, v.re});
-    } else if constexpr (NTS && PIFFT_NT_STORES && vec_nt<T>()) {
+    } else if constexpr (NTS && vec_nt<T>()) {
         vec2_t<T> r;
         r.x = v.re;
         r.y = v.im;
         __builtin_nontemporal_store(r, reinterpret_cast<vec2_t<T>*>(p));
-    } else if constexpr (NTS && PIFFT_NT_STORES) {
+    } else if constexpr (NTS) {
         __builtin_nontemporal_store(v.re, &p->re);
         __builtin_nontemporal_store(v.im, &p->im);
     } else {
         *p = v;
     }
 }
-// PIFFT_CLAMP_LOADS: a partial last tile's idle lanes load the last line again
-// (unconditional loads, no per-load branch; 1: both precisions, 2: fp32 only)
-// instead of skipping their loads (same measurements: fp32 only, 2)
-#ifndef PIFFT_CLAMP_LOADS
-#define PIFFT_CLAMP_LOADS 2
-#endif
+// clamp_loads: a partial last tile's idle lanes load the last line again
+// (unconditional loads, no per-load branch) instead of skipping their loads
+// (same measurements: a gain for fp32 only)
 template <typename T>
 constexpr bool clamp_loads() {
-    return PIFFT_CLAMP_LOADS == 1 || (PIFFT_CLAMP_LOADS == 2 && sizeof(T) == 4);
+    return sizeof(T) == 4;
 }
 
 // two-level twiddle: w_M^E = hi[E >> h] * lo[E & (2^h - 1)]
@@ -590,12 +589,10 @@ struct PassShape {
 template <int R, int C, int VPT = 16>
 struct PassCfg {
     static constexpr int NT = C * R / PassShape<R, VPT>::Q;
-#ifndef PIFFT_MIN_WG_PER_CU
-#define PIFFT_MIN_WG_PER_CU 2
-#endif
-    // register budget: PIFFT_MIN_WG_PER_CU workgroups resident per CU, but
+    // register budget: min_wg_per_cu workgroups resident per CU, but
     // never under 128 VGPRs (4 waves/SIMD): 16 complex values + twiddles
-    static constexpr int wpe = NT >= 256 ? (NT * PIFFT_MIN_WG_PER_CU) / 256 : 1;
+    static constexpr int min_wg_per_cu = 2;
+    static constexpr int wpe = NT >= 256 ? (NT * min_wg_per_cu) / 256 : 1;
     static constexpr int waves_per_eu = wpe > 4 ? 4 : wpe;
 };
 
@@ -670,22 +667,19 @@ struct Stage {
     static constexpr int NB = R / q;
     static constexpr int ns = 1 << (Sh::LOGB * S);
     static constexpr bool cfast = first ? (MODE != 0) : (last ? (MODE == 2) : false);  // MODE 3 as MODE 1
-#ifndef PIFFT_WAVE_PRIVATE
-#define PIFFT_WAVE_PRIVATE 3  // bit 0: whole-line stages (a), bit 1: beta groups (b)
-#endif
     // Wave-private exchanges (no workgroup barrier into this stage).
     // (a) b-fast stage after a b-fast radix-16 stage (one butterfly per
     //     thread) whose R/16 butterflies per line divide 64: every wave holds
     //     whole lines, and this stage keeps each wave on the same lines.
     static constexpr int NBP = R / 16;
-    static constexpr bool whole_lines = (PIFFT_WAVE_PRIVATE & 1) && !first && !cfast && (S >= 2 || MODE == 0) &&
+    static constexpr bool whole_lines = !first && !cfast && (S >= 2 || MODE == 0) &&
                                         Sh::Q == 16 && NBP <= 64 && 64 % NBP == 0 && NT % 64 == 0;
     static constexpr int LPW = whole_lines ? 64 / NBP : 1;  // lines per wave
     // (b) MODE 2, three stages, middle + (c-fast) last stage: last-stage
     //     butterflies beta + 16 m (m < 16) read exactly the outputs of the
     //     middle-stage butterflies beta + 16 k (k < QL).  A wave owns the same
     //     beta groups on all C lines in both stages (lanes across lines).
-    static constexpr bool grouped = (PIFFT_WAVE_PRIVATE & 2) && MODE == 2 && Sh::NSTG == 3 && S >= 1 && Sh::Q == 16 &&
+    static constexpr bool grouped = MODE == 2 && Sh::NSTG == 3 && S >= 1 && Sh::Q == 16 &&
                                     64 % C == 0 && (64 / C) % Sh::QL == 0 && NT % 64 == 0;
     static constexpr int GPW = grouped ? 64 / (C * Sh::QL) : 1;  // beta groups per wave
     static constexpr bool wave_private = whole_lines || (grouped && last);
@@ -698,7 +692,6 @@ struct Stage {
     //     NBP = 32 (R = 512) a 2x2 transpose of register pairs across row
     //     pairs: cross-lane v_permlane32_swap / v_permlane16_swap (CDNA4)
     //     instead of an LDS store + load per component.
-    //     PIFFT_PERMLANE bit 0: radix 2 (R = 512), bit 1: radix 4 (R = 1024).
     //     Measured on MI355X (tools/gpu_round.sh perm): radix 2 in the fused
     //     tree pass ~0.5 % faster.  Radix 4 cost 2 spills and 5.5 % in round
     //     1's C4 first pass; since round 3 it compiles spill-free wherever
@@ -708,13 +701,9 @@ struct Stage {
     //     VGPRs (round 5, every instance's gfx950 register metadata with and
     //     without it) -- so it is on there only (perm4_ok).  Config 1 +0.5-1 %
     //     (profiles/r04c_permlane4_c1.log), bitwise equal to the LDS path.
-#ifndef PIFFT_PERMLANE
-#define PIFFT_PERMLANE 3
-#endif
     static constexpr bool perm4_ok = C <= 4 || MODE == 1;
     static constexpr bool perm = last && !first && !cfast && Sh::Q == 16 && NT % 64 == 0 && Sh::NSTG == 3 &&
-                                 (((PIFFT_PERMLANE & 2) && q == 4 && NBP == 64 && perm4_ok) ||
-                                  ((PIFFT_PERMLANE & 1) && q == 2 && NBP == 32));
+                                 ((q == 4 && NBP == 64 && perm4_ok) || (q == 2 && NBP == 32));
     __host__ __device__ static __forceinline__ void map(int tid, int u, int& c, int& b) {
         if constexpr (perm) {
             const int lane = tid & 63;
@@ -785,75 +774,48 @@ __device__ __forceinline__ void pl_swap(cx<T>& a, cx<T>& b) {
     __builtin_memcpy(&b, y, sizeof b);
 }
 
-// Stage twiddles fetched with the data (PIFFT_TW_PREFETCH): the anchors of
-// every later stage's butterflies are loaded right after the tile's inputs
-// are issued (all of w, w^2, w^4, w^8, or only w with the others formed by
-// squaring when the stage runs) -- instead of 2-4 table loads at the start
-// of each stage, each a
-// dependent round trip on a workgroup's critical path.  That path is what
-// bounds the latency-bound small launches (one or two workgroups per CU);
-// the streaming passes hide it behind the other workgroup.
-// 0: off; 1: single passes (MODE 0/4) only; 2: every pass; 3: single and
-// first passes (MODE 0/1) of tiles built for at most 2 waves per SIMD (a
-// budget of 256 VGPRs), every anchor w, w^2, w^4, w^8 fetched from the table
-// (the values the stage would load itself: bitwise equal to 0; the 128-VGPR
-// instances would spill 4-46 VGPRs).
-// Measured on MI355X (profiles/r02_ab_twiddle_prefetch.log): no gain on the
-// small launches (fp32 4096 x 512: 9 us either way; fp64 2^20: 24 us either
-// way), fp64 8192 x 64 single passes 11 -> 15 us (registers), C4 +3 % at 2 --
-// so off; round 6 (profiles/r06s_*): at 2, config 3's single pass 47 -> 45
-// us and the first passes of C1 / C4 1-2 % faster, config 2's and C4's
-// later passes 3-11 % slower (spills at 128 VGPRs) -- hence 3, the default
-// since round 6 (profiles/r06t_*: outputs bitwise equal to 0 on 15 plans;
-// config 3 +1.4 %, config 1 +0.9 %, fp64 4096 x 1024 +5.5 %, fp64 2^22 +1.2 %,
-// configs 2 and 4 tie).
-#ifndef PIFFT_DIAG_NO_XCHG
-#define PIFFT_DIAG_NO_XCHG 0  // diagnostics: skip the LDS hand-offs between stages (timing only)
-#endif
-#ifndef PIFFT_TW_PREFETCH
-#define PIFFT_TW_PREFETCH 3
-#endif
-template <int R, int C, int BM, int VPT>
-constexpr bool tw_prefetch() {
-    return PIFFT_TW_PREFETCH == 2 || (PIFFT_TW_PREFETCH == 1 && BM == 0) ||
-           (PIFFT_TW_PREFETCH == 3 && (BM == 0 || BM == 1) && PassCfg<R, C, VPT>::waves_per_eu <= 2);
-}
-// anchors fetched per butterfly of a radix-q stage: all log2 q (3), or the
-// base one, the others formed by squaring (1, 2)
-template <int q>
-constexpr int pre_anchors() { return PIFFT_TW_PREFETCH == 3 ? ilog2c(q) : 1; }
+// Stage twiddles fetched with the data: the anchors w, w^2, w^4, w^8 of every
+// later stage's butterflies (log2 q table entries per radix-q butterfly, the
+// values the stage would load itself: bitwise equal) are loaded right after
+// the tile's inputs are issued -- instead of 2-4 table loads at the start of
+// each stage, each a dependent round trip on a workgroup's critical path.
+// That path is what bounds the latency-bound small launches (one or two
+// workgroups per CU); the streaming passes hide it behind the other workgroup.
+// Which instances do it: pass_tw_prefetch, below.
 // anchors of stages 1 .. S-1
 template <int R, int C, int BM, int VPT, int S>
 constexpr int pre_offset() {
     if constexpr (S <= 1) return 0;
     else return pre_offset<R, C, BM, VPT, S - 1>() +
-                Stage<R, C, BM, S - 1, VPT>::U * pre_anchors<Stage<R, C, BM, S - 1, VPT>::q>();
+                Stage<R, C, BM, S - 1, VPT>::U * ilog2c(Stage<R, C, BM, S - 1, VPT>::q);
 }
 template <int R, int C, int BM, int VPT>
 constexpr int pre_count() {
     return pre_offset<R, C, BM, VPT, PassShape<R, VPT>::NSTG>();
 }
 
-// Workgroups per CU a k_pass instance is built for: two (PIFFT_MIN_WG_PER_CU),
+// Workgroups per CU a k_pass instance is built for: two (PassCfg::min_wg_per_cu),
 // one for the fused tree pass at P = 16 (its 16 leaves per input)
 // (config 3's single pass built for 8 waves per SIMD -- 64 VGPRs, 8 of its 16
 // workgroups per CU at once instead of 7 -- spills 18 B per lane and runs
 // 70 % slower: round 4, profiles/r04f_c3_wpe8.log)
-template <typename T, int R, int C, int MODE, int LP, int VPT>
+template <int R, int C, int MODE, int LP, int VPT>
 constexpr int pass_waves_per_eu() {
     constexpr int w = PassCfg<R, C, VPT>::waves_per_eu;
     return ((MODE & 3) == 3 && LP >= 5) ? 1 : ((MODE & 3) == 3 && LP >= 4 && w > 2) ? 2 : w;
 }
-// The stage-twiddle prefetch of a k_pass instance: tw_prefetch, and (at 3)
-// the one-worker fused tree pass (MODE 3) of 256-VGPR tiles as well -- round 6
-// (profiles/r06y5_*): config 2's one-GPU slice +1.9 %, bitwise equal; the
-// all-worker fused pass (MODE 11) measured 0.3 % slower with it, so not there.
-template <typename T, int R, int C, int MODE, int LP, int VPT>
+// The stage-twiddle prefetch of a k_pass instance: single passes, first passes
+// and the one-worker fused tree pass (MODE & 3 = 0, 1, 3) of tiles built for
+// at most 2 waves per SIMD (a budget of 256 VGPRs), and not the all-worker
+// fused pass (MODE 11).  The 128-VGPR instances would spill 4-46 VGPRs with
+// it, and the later passes (MODE 2) ran 3-11 % slower
+// (profiles/r02_ab_twiddle_prefetch.log, profiles/r06s_*); as it is, config 3
+// +1.4 %, config 1 +0.9 %, fp64 4096 x 1024 +5.5 %, outputs bitwise equal on
+// 15 plans (profiles/r06t_*), config 2's one-GPU slice +1.9 % in MODE 3 and
+// MODE 11 0.3 % slower with it (profiles/r06y5_*).  The history: DESIGN.md.
+template <int R, int C, int MODE, int LP, int VPT>
 constexpr bool pass_tw_prefetch() {
-    if constexpr (PIFFT_TW_PREFETCH == 3 && (MODE & 3) == 3 && !(MODE & 8) &&
-                  pass_waves_per_eu<T, R, C, MODE, LP, VPT>() <= 2)
-        return true;
-    return tw_prefetch<R, C, MODE & 3, VPT>();
+    return (MODE & 3) != 2 && MODE != 11 && pass_waves_per_eu<R, C, MODE, LP, VPT>() <= 2;
 }
 
 // MODE 11 = 3 | 8: the tree of ALL P = 2^LP workers fused into the first
@@ -934,7 +896,7 @@ __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>
     // every level's twiddles in one round trip beside the leaves (where the
     // instance has the registers: <= 2 waves per SIMD, i.e. the latency-bound
     // small tiles; the 128-VGPR streaming instances would spill)
-    constexpr bool PRE = pass_waves_per_eu<T, R, C, 11, LP, VPT>() <= 2;
+    constexpr bool PRE = pass_waves_per_eu<R, C, 11, LP, VPT>() <= 2;
     TreeTwRegs<T, LP> trw[PRE ? PPT : 1];
     if constexpr (PRE) {
 #pragma unroll
@@ -975,12 +937,10 @@ __device__ __forceinline__ void wil_tree_to_lds(const PassArgs& a, T* lds, cx<T>
     }
 }
 
-#ifndef PIFFT_SERIAL_BFLY
-#define PIFFT_SERIAL_BFLY 1
-#endif
 template <typename T, int R, int C, int MODE, int NTS, int LP, int S, int VPT, int SW = 0>
 __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v, cx<T>* pre, int tid, uint64_t tile,
                                             cx<T>* twp) {
+    static_assert(PassShape<R, VPT>::Q <= 16, "more than 16 values per thread: pass_stages_packed (fp32 VPT 32)");
     using C2 = cx<T>;
     // MODE | 4: the same pass storing at bitrev_{log2 M}(natural position),
     // the reference's scratch order (PIFFT_OUT_BITREV; last pass only).  Each
@@ -995,12 +955,6 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
     using Sh = PassShape<R, VPT>;
     constexpr int q = St::q, U = St::U, NB = St::NB, ns = St::ns;
     constexpr LdsLayout LL = LdsPick<T, R, C, SM, VPT>::value;
-    // Several butterflies per thread (VPT 32): one after the other, each with
-    // its own twiddles, loads and stores -- scheduling barriers keep the
-    // compiler from interleaving their temporaries and hoisting their
-    // addresses (two concurrent radix-16 DFTs spill at the 128-VGPR budget of
-    // two workgroups per CU)
-    constexpr bool serial = U > 1 && Sh::Q > 16 && PIFFT_SERIAL_BFLY;
     // (run-time even where the mode fixes them -- M/R = 1 for a single pass,
     // Ns = 1 for a first pass: compile-time values measured 2 % slower there)
     const uint32_t log_lb = a.log_lb;
@@ -1020,7 +974,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
     // multiple of C: c does not depend on u) the step factor w^{jm NB} is
     // shared: fetched once, for u = 0.
     constexpr bool share_anc = St::cfast && U > 1 && St::NT % C == 0;
-    [[maybe_unused]] C2* tw_pre = twp;  // 4 U entries (k_pass: first_tw_count)
+    // (twp: 4 U entries, k_pass: first_tw_count)
     if constexpr (St::first && BM == 2) {
         const C2* tlo = static_cast<const C2*>(a.tw_lo);
         const C2* thi = static_cast<const C2*>(a.tw_hi);
@@ -1032,11 +986,11 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             const uint64_t jm = (((tile * C + c) & lb_mask) >> wil) & ns_mask;
             const uint64_t e0 = (jm * (uint64_t)NB) << a.tw_shift, e1 = (jm * (uint64_t)b) << a.tw_shift;
             if (!share_anc || u == 0) {
-                tw_pre[4 * u + 0] = tlo[e0 & hmask];
-                tw_pre[4 * u + 1] = thi[e0 >> a.tw_h];
+                twp[4 * u + 0] = tlo[e0 & hmask];
+                twp[4 * u + 1] = thi[e0 >> a.tw_h];
             }
-            tw_pre[4 * u + 2] = tlo[e1 & hmask];
-            tw_pre[4 * u + 3] = thi[e1 >> a.tw_h];
+            twp[4 * u + 2] = tlo[e1 & hmask];
+            twp[4 * u + 3] = thi[e1 >> a.tw_h];
         }
     }
     if constexpr (St::first && BM == 3 && WIL) {
@@ -1055,11 +1009,10 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             const bool ok = CL || tile * C + c < a.nlines;
             const uint64_t line = (!CL || tile * C + c < a.nlines) ? tile * C + c : a.nlines - 1;
             const uint64_t bt = line >> lbi, j = line & lb_mask;
-            const uint32_t les = lbi;
             // MODE 3: transform bt is worker (bt mod nq) of batch bt / nq, and
             // the leaves come from that batch's input
             const uint64_t bin = BM == 3 ? (bt >> a.log_nq) : bt;
-            const C2* src = in + bin * a.in_bstride + j + ((uint64_t)b << les);
+            const C2* src = in + bin * a.in_bstride + j + ((uint64_t)b << lbi);
             if constexpr (BM == 3) {
                 static_assert(!WIL, "the fused tree pass is slice-major only");
                 // z_q[zi] from the P leaves x[zi + m M] (M = 2^(log_lb + LOGR)),
@@ -1069,13 +1022,9 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                 // slice, 64 workgroups) keep more leaves in flight, so fewer
                 // dependent rounds of loads
                 constexpr int P = 1 << LP;
-#ifndef PIFFT_TREE_LOADS
-#define PIFFT_TREE_LOADS 8  // leaf loads in flight per thread and round
-#endif
-#ifndef PIFFT_TREE_LOADS_SMALL
-#define PIFFT_TREE_LOADS_SMALL 16  // the same for tiles of <= 256 threads
-#endif
-                constexpr int TL = PassCfg<R, C, VPT>::NT <= 256 ? PIFFT_TREE_LOADS_SMALL : PIFFT_TREE_LOADS;
+                constexpr int tree_loads = 8;         // leaf loads in flight per thread and round
+                constexpr int tree_loads_small = 16;  // the same for tiles of <= 256 threads
+                constexpr int TL = PassCfg<R, C, VPT>::NT <= 256 ? tree_loads_small : tree_loads;
                 constexpr int G0 = P >= TL ? 1 : TL / P;
                 constexpr int G = G0 > q ? q : G0;  // (at most one round per value)
                 static_assert(q % G == 0, "whole rounds of leaf loads");
@@ -1105,8 +1054,8 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                     __builtin_amdgcn_sched_barrier(0);  // next round's leaves after this one's trees
                 });
             } else if constexpr (BM == 2) {
-                // rows 2^les + in_pad apart (padded workspace, PassArgs::in_pad)
-                const uint64_t rs = (1ull << les) + a.in_pad;
+                // rows 2^lbi + in_pad apart (padded workspace, PassArgs::in_pad)
+                const uint64_t rs = (1ull << lbi) + a.in_pad;
                 const C2* row = in + bin * a.in_bstride + j + (uint64_t)b * rs;
 #pragma unroll
                 for (int k = 0; k < q; k++)
@@ -1114,12 +1063,12 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             } else {
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << les)) : C2{(T)0, (T)0};
+                    v[u * q + k] = ok ? ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << lbi)) : C2{(T)0, (T)0};
             }
         }
     }
     if constexpr (St::first) PIFFT_WGC(3);
-    if constexpr (St::first && pass_tw_prefetch<T, R, C, MODE, LP, VPT>()) {
+    if constexpr (St::first && pass_tw_prefetch<R, C, MODE, LP, VPT>()) {
         const C2* __restrict__ twr = static_cast<const C2*>(a.tw_r);
         static_for<1, Sh::NSTG, 1>([&](auto sc) {
             constexpr int S2 = decltype(sc)::value;
@@ -1128,7 +1077,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             for (int u = 0; u < St2::U; u++) {
                 int c, b;
                 St2::map(tid, u, c, b);
-                constexpr int NA = pre_anchors<St2::q>();
+                constexpr int NA = ilog2c(St2::q);
                 const int e1 = (b & (St2::ns - 1)) * (R / (St2::ns * St2::q));
 #pragma unroll
                 for (int i = 0; i < NA; i++) pre[pre_offset<R, C, SM, VPT, S2>() + u * NA + i] = twr[e1 << i];
@@ -1144,18 +1093,11 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
         for (int u = 0; u < U; u++) {
             if (!share_anc || u == 0) {
                 const int uu = share_anc ? 0 : u;
-                anc[0] = cmul(tw_pre[4 * uu + 1], tw_pre[4 * uu + 0]);  // = tw2(lo, hi, h, jm NB)
+                anc[0] = cmul(twp[4 * uu + 1], twp[4 * uu + 0]);  // = tw2(lo, hi, h, jm NB)
 #pragma unroll
                 for (int i = 1; (1 << i) < q; i++) anc[i] = cmul(anc[i - 1], anc[i - 1]);
             }
             apply_powers<q>(&v[u * q], anc);
-            if constexpr (serial) {
-                dft<q>(&v[u * q]);
-                const C2 base = cmul(tw_pre[4 * u + 3], tw_pre[4 * u + 2]);  // = tw2(lo, hi, h, jm b)
-#pragma unroll
-                for (int k = 0; k < q; k++) v[u * q + k] = cmul(v[u * q + k], base);
-                __builtin_amdgcn_sched_barrier(0);
-            }
         }
     }
     if constexpr (!St::first) {
@@ -1167,12 +1109,10 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             St::map(tid, u, c, b);
             const int e1 = (b & (ns - 1)) * (R / (ns * q));
             C2 anc[4];
-            if constexpr (pass_tw_prefetch<T, R, C, MODE, LP, VPT>()) {
-                constexpr int NA = pre_anchors<q>();
+            if constexpr (pass_tw_prefetch<R, C, MODE, LP, VPT>()) {
+                constexpr int NA = ilog2c(q);
 #pragma unroll
                 for (int i = 0; i < NA; i++) anc[i] = pre[pre_offset<R, C, SM, VPT, S>() + u * NA + i];
-#pragma unroll
-                for (int i = NA; (1 << i) < q; i++) anc[i] = cmul(anc[i - 1], anc[i - 1]);
             } else {
 #pragma unroll
                 for (int i = 0; (1 << i) < q; i++) anc[i] = twr[e1 << i];
@@ -1180,17 +1120,12 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             apply_powers<q>(&v[u * q], anc);
         }
     }
-    if constexpr (!(St::first && BM == 2 && serial)) {
+#pragma unroll
+    for (int u = 0; u < U; u++) dft<q>(&v[u * q]);
+    if constexpr (St::first && BM == 2) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            dft<q>(&v[u * q]);
-            if constexpr (serial) __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if constexpr (St::first && BM == 2 && !serial) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const C2 base = cmul(tw_pre[4 * u + 3], tw_pre[4 * u + 2]);  // = tw2(lo, hi, h, jm b)
+            const C2 base = cmul(twp[4 * u + 3], twp[4 * u + 2]);  // = tw2(lo, hi, h, jm b)
 #pragma unroll
             for (int k = 0; k < q; k++) v[u * q + k] = cmul(v[u * q + k], base);
         }
@@ -1208,14 +1143,14 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             if (line < a.nlines) {
                 const uint64_t bt = line >> lbi, lj = line & lb_mask;
                 const uint64_t j = lj >> wil;  // the worker's own line
-                const uint32_t lns = (uint32_t)log_ns;
-                const uint64_t pos = ((j >> lns) << (lns + Sh::LOGR)) + (j & ((1ull << lns) - 1)) + ((uint64_t)b << lns);
+                const uint64_t pos =
+                    ((j >> log_ns) << (log_ns + Sh::LOGR)) + (j & ((1ull << log_ns) - 1)) + ((uint64_t)b << log_ns);
                 if constexpr (WIL) {
                     // worker q at slot q (or bitrev(q): the natural-order result)
                     const uint32_t wq = (uint32_t)(lj & ((1ull << wil) - 1));
                     const uint64_t slot = a.wbrev ? (uint64_t)(__builtin_bitreverse32(wq) >> (32 - wil)) : wq;
                     C2* dst = out + bt * a.out_bstride + (pos << wil) + slot;
-                    const uint32_t ks = lns + wil;
+                    const uint32_t ks = log_ns + wil;
 #pragma unroll
                     for (int k = 0; k < q; k++) st_stream<nt_stores(NTS), SW>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
                 } else if constexpr (!BREV) {
@@ -1225,16 +1160,15 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
                     // (out_pad: the line block's offset in a padded workspace)
                     const uint64_t pad = (j >> a.out_pad_log) * a.out_pad;
                     C2* dst = out + (bt >> il) * a.out_bstride + rq + (pos << il) + pad;
-                    const uint32_t ks = lns + il;
+                    const uint32_t ks = log_ns + il;
 #pragma unroll
                     for (int k = 0; k < q; k++) st_stream<nt_stores(NTS), SW>(dst + ((uint64_t)(k * NB) << ks), v[u * q + k]);
-                    if constexpr (serial && PIFFT_SERIAL_BFLY >= 2) __builtin_amdgcn_sched_barrier(0);
                 } else {
                     C2* dst = out + bt * a.out_bstride;
                     const uint32_t sh = 64 - (log_lb + Sh::LOGR);  // log2 M bits
 #pragma unroll
                     for (int k = 0; k < q; k++) {
-                        const uint64_t pk = pos + ((uint64_t)(k * NB) << lns);
+                        const uint64_t pk = pos + ((uint64_t)(k * NB) << log_ns);
                         if constexpr (SW & 2) dst[sh < 64 ? __builtin_bitreverse64(pk) >> sh : 0] = sw_out<SW>(v[u * q + k]);
                         else dst[sh < 64 ? __builtin_bitreverse64(pk) >> sh : 0] = v[u * q + k];
                     }
@@ -1259,11 +1193,6 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             for (int g = 0; g < 8; g++) pl_swap<16>(v[2 * g], v[2 * g + 1]);
         }
         pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT, SW>(a, lds, v, pre, tid, tile, twp);
-    } else if constexpr (PIFFT_DIAG_NO_XCHG && MODE != 11) {
-        // diagnostics build only (timing, WRONG results): no hand-off at all --
-        // the upper bound of what any register exchange (DPP, ds_swizzle,
-        // permlane) could save on this pass (round 6, profiles/sessions/gpu_r06w.sh)
-        pass_stages<T, R, C, MODE, NTS, LP, S + 1, VPT, SW>(a, lds, v, pre, tid, tile, twp);
     } else {
         // ---- exchange with stage S+1 through LDS, one component at a time ----
         using Nx = Stage<R, C, SM, S + 1, VPT>;
@@ -1273,11 +1202,10 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
             // MODE 11's first stage has just read its inputs from LDS and
             // waited for every thread's reads)
             if (S > 0 || comp > 0) lds_handoff<Nx::wave_private>();
-            const int tidc = tid;
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 int c, b;
-                St::map(tidc, u, c, b);
+                St::map(tid, u, c, b);
                 const int base = (b / ns) * ns * q + (b & (ns - 1));  // r' = base + k ns
 #pragma unroll
                 for (int k = 0; k < q; k++) lds[lds_at(LL, c, base + k * ns)] = comp ? v[u * q + k].im : v[u * q + k].re;
@@ -1286,7 +1214,7 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
 #pragma unroll
             for (int u = 0; u < Nx::U; u++) {
                 int c, b;
-                Nx::map(tidc, u, c, b);
+                Nx::map(tid, u, c, b);
 #pragma unroll
                 for (int k = 0; k < Nx::q; k++) {
                     const T x = lds[lds_at(LL, c, b + k * Nx::NB)];
@@ -1306,31 +1234,11 @@ __device__ __forceinline__ void pass_stages(const PassArgs& a, T* lds, cx<T>* v,
 // even butterfly, .y the odd one), so their arithmetic is v_pk_add_f32 /
 // v_pk_mul_f32 on pairs -- the same operations in the same order as two
 // scalar butterflies (bitwise equal), with the register state of ONE fp64
-// butterfly instead of two interleaved fp32 ones (the scalar VPT-32 form wants
-// 174 VGPRs in MODE 2 and spills at 128).  Loads, stores and LDS exchanges
-// address each half with the VPT-32 Stage map of its own butterfly.
+// butterfly instead of two interleaved fp32 ones (a scalar VPT-32 form wanted
+// 174 VGPRs in MODE 2 and spilled at 128; this is the only VPT-32 form, and
+// pass_stages holds at most 16 values per thread).  Loads, stores and LDS
+// exchanges address each half with the VPT-32 Stage map of its own butterfly.
 // ---------------------------------------------------------------------------
-// Diagnostics builds only (timing, WRONG results; never the product): the
-// packed fp32 passes without their twiddles (PIFFT_DIAG_NO_TW=1: no table
-// loads, no twiddle products) or without their butterflies
-// (PIFFT_DIAG_NO_DFT=1), to split a pass's time between its data movement,
-// LDS exchanges, twiddles and arithmetic (round 6, profiles/sessions/gpu_r06g.sh).
-#ifndef PIFFT_DIAG_NO_TW
-#define PIFFT_DIAG_NO_TW 0
-#endif
-#ifndef PIFFT_DIAG_NO_DFT
-#define PIFFT_DIAG_NO_DFT 0
-#endif
-template <int q, typename V>
-__device__ __forceinline__ void dft_diag(V* v) {
-    if constexpr (!PIFFT_DIAG_NO_DFT) dft<q>(v);
-}
-#ifndef PIFFT_PK_SERIAL
-#define PIFFT_PK_SERIAL 0  // packed passes: a scheduling barrier after each butterfly pair (tuning A/B)
-#endif
-#ifndef PIFFT_PK_REMAT
-#define PIFFT_PK_REMAT 1  // packed VPT-32 exchanges: LDS addresses recomputed per component
-#endif
 using f2 = float __attribute__((ext_vector_type(2)));
 
 template <int H>
@@ -1374,7 +1282,7 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
     constexpr bool share_anc = St::cfast && U > 1 && St::NT % C == 0;
 
     if constexpr (St::first) {
-        if constexpr (BM == 2 && !PIFFT_DIAG_NO_TW) {
+        if constexpr (BM == 2) {
             const C1* tlo = static_cast<const C1*>(a.tw_lo);
             const C1* thi = static_cast<const C1*>(a.tw_hi);
             const uint64_t hmask = (1ull << a.tw_h) - 1;
@@ -1400,23 +1308,22 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
             St::map(tid, u, c, b);
             const uint64_t line = tile * C + c < a.nlines ? tile * C + c : a.nlines - 1;
             const uint64_t bt = line >> log_lb, j = line & lb_mask;
-            const uint32_t les = log_lb;
             if constexpr (BM == 2) {
-                const uint64_t rs = (1ull << les) + a.in_pad;
+                const uint64_t rs = (1ull << log_lb) + a.in_pad;
                 const C1* row = in + bt * a.in_bstride + j + (uint64_t)b * rs;
 #pragma unroll
                 for (int k = 0; k < q; k++)
                     pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS), SW>(row + (uint64_t)(k * NB) * rs));
             } else {
-                const C1* src = in + bt * a.in_bstride + j + ((uint64_t)b << les);
+                const C1* src = in + bt * a.in_bstride + j + ((uint64_t)b << log_lb);
 #pragma unroll
                 for (int k = 0; k < q; k++)
-                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << les)));
+                    pk_put<u & 1>(vp[(u >> 1) * q + k], ld_stream<nt_loads(NTS), SW>(src + ((uint64_t)(k * NB) << log_lb)));
             }
         });
     }
     // ---- twiddles and butterflies, one packed pair of butterflies at a time ----
-    if constexpr (St::first && BM == 2 && !PIFFT_DIAG_NO_TW) {
+    if constexpr (St::first && BM == 2) {
         C1 anc0[4], anc1[4];
         if constexpr (share_anc) {
             anc0[0] = cmul(twp[1], twp[0]);
@@ -1438,14 +1345,13 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
 #pragma unroll
             for (int i = 0; (1 << i) < q; i++) ap[i] = pk_pair(anc0[i], share_anc ? anc0[i] : anc1[i]);
             apply_powers<q>(&vp[m * q], ap);
-            dft_diag<q>(&vp[m * q]);
-            if constexpr (PIFFT_PK_SERIAL) __builtin_amdgcn_sched_barrier(0);
+            dft<q>(&vp[m * q]);
             const CP base = pk_pair(cmul(twp[4 * (2 * m) + 3], twp[4 * (2 * m) + 2]),
                                     cmul(twp[4 * (2 * m + 1) + 3], twp[4 * (2 * m + 1) + 2]));
 #pragma unroll
             for (int k = 0; k < q; k++) vp[m * q + k] = cmul(vp[m * q + k], base);
         }
-    } else if constexpr (!St::first && !PIFFT_DIAG_NO_TW) {
+    } else if constexpr (!St::first) {
         // w_{ns q}^{(b mod ns) k} = w_R^{(b mod ns) k R/(ns q)}, per butterfly
         const C1* __restrict__ twr = static_cast<const C1*>(a.tw_r);
 #pragma unroll
@@ -1458,14 +1364,12 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
 #pragma unroll
             for (int i = 0; (1 << i) < q; i++) ap[i] = pk_pair(twr[e0 << i], twr[e1 << i]);
             apply_powers<q>(&vp[m * q], ap);
-            dft_diag<q>(&vp[m * q]);
-            if constexpr (PIFFT_PK_SERIAL) __builtin_amdgcn_sched_barrier(0);
+            dft<q>(&vp[m * q]);
         }
     } else {
 #pragma unroll
         for (int m = 0; m < U / 2; m++) {
-            dft_diag<q>(&vp[m * q]);
-            if constexpr (PIFFT_PK_SERIAL) __builtin_amdgcn_sched_barrier(0);
+            dft<q>(&vp[m * q]);
         }
     }
 
@@ -1500,7 +1404,7 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
             // beside the 64 data registers (they spilled 52 B per lane in the
             // 1024-point MODE 2 instance)
             int tidc = tid;
-            if (PIFFT_PK_REMAT && comp) asm volatile("" : "+v"(tidc));
+            if (comp) asm volatile("" : "+v"(tidc));
             static_for<0, U, 1>([&](auto uc) {
                 constexpr int u = decltype(uc)::value;
                 int c, b;
@@ -1533,9 +1437,6 @@ __device__ __forceinline__ void pass_stages_packed(const PassArgs& a, float* lds
     }
 }
 
-#ifndef PIFFT_PACK32
-#define PIFFT_PACK32 1  // VPT-32 fp32 instances: the packed form (0: the scalar form, which spills)
-#endif
 // inter-pass twiddle entries fetched with a tile's first-stage loads (MODE 2)
 template <int R, int C, int MODE, int VPT>
 constexpr int first_tw_count() {
@@ -1589,12 +1490,11 @@ constexpr int first_tw_count() {
     T* lds = reinterpret_cast<T*>(pifft_smem);                                                                       \
     const int tid = (int)threadIdx.x;                                                                                \
     PIFFT_WGC_ENTRY();                                                                                               \
-    if constexpr (VPT == 32 && std::is_same_v<T, float> && PIFFT_PACK32) {                                           \
+    if constexpr (VPT == 32) {                                                                                       \
+        static_assert(std::is_same_v<T, float>, "VPT 32 is fp32 only (pass_stages_packed)");                         \
         cx<f2> vp[PassShape<R, VPT>::Q / 2];                                                                         \
         cx<float> twp[TWN];                                                                                          \
         pass_stages_packed<R, C, MODE, NTS, 0, SW>(a, reinterpret_cast<float*>(pifft_smem), vp, tid, tile, twp);     \
-        (void)pre;                                                                                                   \
-        (void)lds;                                                                                                   \
     } else {                                                                                                         \
         if (a.ilv_log && a.log_lb >= (uint32_t)ilog2c(C)) {                                                          \
             const uint32_t il = a.ilv_log, ltt = a.log_lb - (uint32_t)ilog2c(C);                                     \
@@ -1608,7 +1508,7 @@ constexpr int first_tw_count() {
     PIFFT_WGC_EXIT()
 
 template <typename T, int R, int C, int MODE, int NTS, int LP, int VPT = 16>
-__global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<T, R, C, MODE, LP, VPT>()))
+__global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<R, C, MODE, LP, VPT>()))
 void k_pass(PassArgs a) {
     PIFFT_PASS_KERNEL_BODY(0);
 }
@@ -1616,7 +1516,7 @@ void k_pass(PassArgs a) {
 // The swapping twin of k_pass<T, R, C, MODE, NTS, LP, VPT> for inverse plans:
 // the same pass with SW's swaps (1: loads of a.in, 2: stores to a.out, 3: both)
 template <typename T, int R, int C, int MODE, int NTS, int LP, int VPT, int SW>
-__global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<T, R, C, MODE, LP, VPT>()))
+__global__ __launch_bounds__((PassCfg<R, C, VPT>::NT), (pass_waves_per_eu<R, C, MODE, LP, VPT>()))
 void k_pass_sw(PassArgs a) {
     static_assert(SW >= 1 && SW <= 3, "k_pass_sw: a swapping twin (the forward kernel is k_pass)");
     PIFFT_PASS_KERNEL_BODY(SW);
@@ -1797,7 +1697,6 @@ constexpr int IL_TILE = 2048;
     const uint32_t log_k = 11 - log_p;                                                                                \
     const uint32_t log_m = log_n - log_p;                                                                             \
     const uint64_t ntiles = total >> 11;                                                                              \
-    const uint32_t P = 1u << log_p;                                                                                   \
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {                                                       \
         const uint64_t e0 = t << 11;                                                                                  \
         const uint64_t bt = e0 >> log_n, k0 = (e0 & ((1ull << log_n) - 1)) >> log_p;                                  \
@@ -1817,7 +1716,6 @@ constexpr int IL_TILE = 2048;
             if constexpr ((SW) & 2) dst[o] = sw_out<(SW)>(tile[o + (o >> 4)]);                                        \
             else dst[o] = tile[o + (o >> 4)];                                                                         \
         }                                                                                                             \
-        (void)P;                                                                                                      \
     }
 template <typename T>
 __global__ __launch_bounds__(256) void k_interleave_tile(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,

@@ -3,7 +3,7 @@
 libpifft (PIFFT_LIB) and write each output's SHA-256 to stdout; two runs with
 two builds, diffed, show whether a kernel change kept the results bit for bit
 (round 6: the one-round-trip tree twiddle fetch, tree_tw_fetch, against the
-round-5 kernels; the stage-twiddle prefetch, PIFFT_TW_PREFETCH=3, against
+round-5 kernels; the stage-twiddle prefetch, pass_tw_prefetch, against
 HEAD's kernels on one-worker plans: --set single; and on one worker's
 slice of a split, the one-worker fused tree pass: --set slice).
 usage: PIFFT_LIB=abvar/x.so python3 tools/bitwise_libs.py [--set tree|single|slice]"""

@@ -73,6 +73,7 @@ for T, prec in (("double", 64), ("float", 32)):
 # workgroups per CU (PIFFT_VPT32; three passes 1024-512-512 at 2^28)
 # (R = 512 and 1024: the radices of 2^27-2^30 three-pass plans; 256 and 2048
 # spill 44-100 B per lane in this form)
+# VPT 32 is float only: the kernels have no other form of it (pass_stages_packed)
 for R in (512, 1024):
     C = 16384 // R
     for nts in (0, 1):

@@ -4,7 +4,7 @@
 // segment M = 2^25, R = 512, C = 16 lines per tile): each of a tile's 8192
 // inputs z[j + r 2^16] sums its P = 8 leaves x[j + r 2^16 + m 2^25] (no
 // twiddles, no FFT), and the tile's 8192 results are stored contiguously.
-// Loads in rounds of G*P leaves per thread (the kernel's PIFFT_TREE_LOADS),
+// Loads in rounds of G*P leaves per thread (the kernel's tree_loads),
 // 512 threads, 2 workgroups per CU like the kernel.  Against the kernel's
 // 0.865-0.876 ms (profiles/r02_rank_plans.log).
 //   hipcc -O3 -w --offload-arch=gfx950 tools/probe_fused.hip -o tools/probe_fused
