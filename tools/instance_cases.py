@@ -174,10 +174,10 @@ def env_text(env) -> str:
     return " ".join(f"{k}={v}" for k, v in env) if env else "-"
 
 
-def write_cases(path: str, rows: list) -> None:
-    """rows: [(Case, covers)]"""
+def write_cases(path: str, rows: list, tool: str = "tools/instance_cases.py") -> None:
+    """rows: [(Case, covers)]; tool: the writer the header line names"""
     with open(path, "w") as f:
-        f.write("# tools/instance_cases.py: n P first count batch prec flags dir env covers(launch:prec/R/C/mode/nts/lp/vpt:SW)\n")
+        f.write(f"# {tool}: n P first count batch prec flags dir env covers(launch:prec/R/C/mode/nts/lp/vpt:SW)\n")
         for c, cov in rows:
             cv = ";".join("%d:%s:%d" % (i, "/".join(str(v) for v in d), sw) for i, d, sw in cov)
             f.write("\t".join(str(v) for v in (c.n, c.P, c.first, c.count, c.batch, c.prec, c.flags,
@@ -437,17 +437,18 @@ def case_id(case: Case) -> str:
             f"{'inv' if case.inverse else 'fwd'}{env}")
 
 
-def figures(log: str, per_line: int = 5) -> str:
+def figures(log: str, per_line: int = 5, label: str = "ins", rows: list | None = None) -> str:
     """The ACC lines of a `pytest -s tests/test_gpu_instances.py` log as a
     table, one entry per case: the table's row (1-based, comment lines not
     counted), the rel-L2 and worst-bin ratios to the oracle's, and the
-    worst-bin bound (the rel-L2 bound is 4 throughout)."""
+    worst-bin bound (the rel-L2 bound is 4 throughout).  label, rows: the ACC
+    lines' label and the table of another file of cases (default: this one's)."""
     import re
-    row_of = {case_id(c): k + 1 for k, (c, _) in enumerate(read_cases())}
+    row_of = {case_id(c): k + 1 for k, (c, _) in enumerate(read_cases() if rows is None else rows)}
     got = {}
     with open(log) as f:
         for ln in f:
-            m = re.search(r"ACC ins (\S+): .*?\(([\d.]+)x\) .*?\(([\d.]+)x\)\s+bounds 4x ([\d.]+)x", ln)
+            m = re.search(r"ACC " + label + r" (\S+): .*?\(([\d.]+)x\) .*?\(([\d.]+)x\)\s+bounds 4x ([\d.]+)x", ln)
             if m:
                 got[row_of[m.group(1)]] = "%4d %4.2f %4.2f %4.2f" % (row_of[m.group(1)], float(m.group(2)),
                                                                        float(m.group(3)), float(m.group(4)))
