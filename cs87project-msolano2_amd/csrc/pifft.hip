@@ -9,6 +9,7 @@
 //             each an LDS-resident R-point sub-FFT over C adjacent lines
 //   [interleave: slice-major -> natural order, whole transform on one GPU]
 //   [real plans: the N/2-point chain above plus one fix-up launch (create_real, pifft_real.h)]
+//   [matrix plans: two such chains, rows and columns, with transposes between them (create_matrix, pifft_matrix.h)]
 //
 // Buffers ping-pong between the caller's output and one plan-owned workspace.
 // Twiddles are host-built tables in HBM (w_R per pass, two-level w_M and w_N;
@@ -19,6 +20,7 @@
 #endif
 #include "pifft_gather.h"
 #include "pifft_kernels.h"
+#include "pifft_matrix.h"
 #include "pifft_planner.h"
 #include "pifft_real.h"
 #include "pifft_table.h"
@@ -195,6 +197,8 @@ const TwinKernel* find_twin(const PassKernel& k, int sw) {
 // from here (find_aux), so none can be launched without being listed, and
 // pifft_aux_count / pifft_aux_desc / pifft_plan_dry_run_aux describe exactly
 // what can be launched (tests/test_aux_cases.py, tests/test_gpu_aux.py).
+// The one exception: the matrix plans' k_transpose, which build_matrix takes
+// from the two-row table of its own in pifft_matrix.h (transpose_fn).
 struct AuxKernel {
     int family, prec, L, sw;  // PIFFT_AUX_*; 32 / 64; tree levels (0: the family has none); 0 or the twin's swaps
     const void* fn;
@@ -255,8 +259,10 @@ const void* find_aux_twin(const void* fn, int sw) {
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
-enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, STEP_R2C_POST = 5, STEP_C2R_PRE = 6 };
-// BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real)
+enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, STEP_R2C_POST = 5, STEP_C2R_PRE = 6,
+       STEP_TRANSPOSE = 7 };
+// BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real); a
+// matrix plan's, batch x n0 x n1 values (build_matrix)
 enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, NBUF = 5 };
 
 // a step's twiddle tables as byte offsets into the plan's blob (kNoTable:
@@ -281,6 +287,7 @@ struct Step {
     uint64_t il_total = 0;
     uint32_t il_log_n = 0, il_log_p = 0;
     RealArgs ra{};  // STEP_R2C_POST / STEP_C2R_PRE
+    TransposeArgs xa{};  // STEP_TRANSPOSE
     StepTables tab;
     uint64_t bytes = 0;
 };
@@ -298,6 +305,11 @@ struct pifft_plan : pifft::PlanShape {  // (the shape it was planned for, pifft_
     uint64_t real_n = 0;
     size_t bytes_z = 0;
     size_t rtw_bytes = 0;  // the fix-up step's two-level w_N table (in the blob, after the inner plan's tw_bytes)
+    // pifft_plan_create_matrix: batch arrays of n0 x n1 values.  The shape
+    // above is (n0 n1, one worker, batch); steps, tables and W are those of
+    // the row and the column chain (build_matrix)
+    bool matrix = false;
+    uint64_t n0 = 0, n1 = 0;
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -749,6 +761,7 @@ int materialise(pifft_plan* p, const TableBuilder& tb) {
     if (!tb.blob.empty()) HIPCHK(hipMemcpy(p->d_tw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
     auto at = [&](size_t off) { return off == kNoTable ? nullptr : (const void*)((const char*)p->d_tw + off); };
     auto resolve = [&](Step& s) {
+        if (s.kind == STEP_TRANSPOSE) return;  // (no table, static LDS)
         TreeTw& tree = s.kind == STEP_TREE ? s.ta.tw : s.pa.tree;
         tree.direct = at(s.tab.tree_direct), tree.lo = at(s.tab.tree_lo), tree.hi = at(s.tab.tree_hi);
         if (s.kind == STEP_R2C_POST || s.kind == STEP_C2R_PRE) s.ra.tw_lo = at(s.tab.lo), s.ra.tw_hi = at(s.tab.hi);
@@ -806,17 +819,24 @@ int make_inverse(pifft_plan* p) {
     return 0;
 }
 
-// choose (pifft_planner.h), lay out the tables, assemble the launches; then,
-// unless dry (pifft_plan_dry_run: no device, no allocation), materialise.
-// real_n: the real length of a real plan (its added launch), else 0
-int build_plan(pifft_plan* p, bool dry, uint64_t real_n = 0) {
+// one chain of launches for the shape p holds: choose (pifft_planner.h), lay
+// out the tables at the end of tb's blob, assemble the launches (an inverse
+// plan: with its twins).  No device, no allocation; a matrix plan runs it
+// twice over one builder (build_matrix)
+int plan_chain(pifft_plan* p, TableBuilder& tb) {
     PlanChoice ch;
     if (choose_plan(*p, ch)) return -1;
-    TableBuilder tb(p->esz);
-    tb.size_only = dry;
     const TableLayout tl = layout_tables(*p, ch, tb);
     p->tw_bytes = tb.size() ? tb.size() : 256;
-    if (assemble_steps(p, ch, tl) || (p->inverse && make_inverse(p))) return -1;
+    return (assemble_steps(p, ch, tl) || (p->inverse && make_inverse(p))) ? -1 : 0;
+}
+// the chain, a real plan's added launch, then, unless dry (pifft_plan_dry_run:
+// no device, no allocation), materialise.
+// real_n: the real length of a real plan (its added launch), else 0
+int build_plan(pifft_plan* p, bool dry, uint64_t real_n = 0) {
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    if (plan_chain(p, tb)) return -1;
     if (real_n) add_real_step(p, tb, real_n, p->inverse);
     return dry ? 0 : materialise(p, tb);
 }
@@ -903,8 +923,123 @@ int create_real(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t batch, 
                           PIFFT_OUT_NATURAL | (c2r ? PIFFT_INVERSE : 0), dry, n);
 }
 
+// Matrix plans (pifft_plan_create_matrix; the kernel in pifft_matrix.h): batch
+// arrays of n0 x n1 values.  The plan is the two complex plans plan_chain makes
+// for the rows, (n1, one worker, batch n0), and the columns, (n0, one worker,
+// batch n1) -- natural order, untouched, PIFFT_INVERSE each on its own -- with
+// k_transpose launches between them, over Z (BUF_Z, batch n0 n1 values):
+//   natural:        [rows: d_in -> Z] [T: Z -> d_out] [columns: d_out -> Z] [T: Z -> d_out]
+//   transposed out: [rows: d_in -> d_out] [T: d_out -> Z] [columns: Z -> d_out]
+// A chain keeps its own ping-pong: where the complex plan uses the caller's
+// output it uses the buffer named above (remap, as add_real_step), and W as
+// ever.  The chains never run concurrently: one W of the larger size.  Both
+// chains' tables go into one blob (one TableBuilder: the second chain's offsets
+// come out rebased), so materialise resolves the spliced steps as any plan's.
+int build_matrix(pifft_plan* p, bool dry) {
+    const bool tout = (p->flags & PIFFT_MATRIX_TRANSPOSED_OUT) != 0;
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    pifft_plan chain[2];  // rows, columns: planned here, never materialised (they own nothing)
+    const uint64_t len[2] = {p->n1, p->n0};
+    for (int c = 0; c < 2; c++) {
+        pifft_plan& q = chain[c];
+        static_cast<PlanShape&>(q) =
+            plan_shape(len[c], 1, 0, 1, (uint32_t)(p->batch * len[1 - c]), p->prec, true, false, false);
+        q.device = -1;
+        q.flags = p->flags & PIFFT_INVERSE;
+        q.inverse = p->inverse;
+        if (plan_chain(&q, tb)) return -1;
+    }
+    p->tw_bytes = tb.size();
+    if (chain[0].npasses + chain[1].npasses > 8)
+        return fail("matrix plan: %d + %d passes exceed the 8 a plan describes", chain[0].npasses, chain[1].npasses);
+    const uint64_t total = (uint64_t)p->batch * p->n0 * p->n1;
+    p->bytes_z = (size_t)total * p->esz;
+    p->bytes_w = std::max(chain[0].bytes_w, chain[1].bytes_w);
+    // a chain's launches with its caller-side buffers renamed
+    auto splice = [&](const pifft_plan& q, int in, int out) {
+        for (Step s : q.steps) {
+            s.src = s.src == BUF_IN ? in : s.src == BUF_OUT ? out : s.src;
+            s.dst = s.dst == BUF_OUT ? out : s.dst;
+            p->steps.push_back(s);
+        }
+        for (int i = 0; i < q.npasses; i++) {
+            p->radix[p->npasses] = q.radix[i];
+            p->lines[p->npasses] = q.lines[i];
+            p->vpt[p->npasses++] = q.vpt[i];
+        }
+        p->wil |= q.wil;
+        p->ilv |= q.ilv;
+    };
+    auto transpose = [&](uint64_t rows, uint64_t cols, int src, int dst) {
+        Step s;
+        s.kind = STEP_TRANSPOSE;
+        s.fn = transpose_fn(p->prec);
+        s.xa = p->prec == PIFFT_F64 ? transpose_args<double>(rows, cols, p->batch)
+                                    : transpose_args<float>(rows, cols, p->batch);
+        s.src = src;
+        s.dst = dst;
+        s.block = dim3(256);
+        s.grid = dim3(stride_grid(s.xa.tiles * 256));  // one workgroup per tile, up to the cap
+        s.bytes = 2 * total * p->esz;
+        p->steps.push_back(s);
+    };
+    if (tout) {
+        splice(chain[0], BUF_IN, BUF_OUT);
+        transpose(p->n0, p->n1, BUF_OUT, BUF_Z);
+        splice(chain[1], BUF_Z, BUF_OUT);
+    } else {
+        splice(chain[0], BUF_IN, BUF_Z);
+        transpose(p->n0, p->n1, BUF_Z, BUF_OUT);
+        splice(chain[1], BUF_OUT, BUF_Z);
+        transpose(p->n1, p->n0, BUF_Z, BUF_OUT);
+    }
+    return dry ? 0 : materialise(p, tb);
+}
+
+int create_matrix(pifft_plan** out, uint64_t n0, uint64_t n1, uint32_t batch, int prec, int device, int flags,
+                  bool dry = false) {
+    if (!out) return fail("plan pointer is NULL");
+    *out = nullptr;
+    if (n0 < 2 || !is_pow2(n0) || n1 < 2 || !is_pow2(n1))
+        return fail("Invalid matrix size (n0 and n1 should be 2^i for i>0)");
+    if (batch == 0) return fail("batch must be >= 1");
+    if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
+    if (flags & ~(PIFFT_INVERSE | PIFFT_MATRIX_TRANSPOSED_OUT))
+        return fail("unknown flags %d (a matrix plan takes PIFFT_INVERSE and PIFFT_MATRIX_TRANSPOSED_OUT)", flags);
+    // (n0, n1 < 2^32 from here on: batch n0 n1 < 2^64)
+    if (std::max(n0, n1) > 0xffffffffull / batch)
+        return fail("matrix plan too large: batch * max(n0, n1) must fit the row transforms' 32-bit batch");
+    if (!dry) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available");
+        if (device < 0 || device >= ndev) return fail("device %d out of range (%d devices)", device, ndev);
+    }
+    pifft_plan* p = new pifft_plan;
+    static_cast<PlanShape&>(*p) = plan_shape(n0 * n1, 1, 0, 1, batch, prec, true, false, false);
+    p->matrix = true;
+    p->n0 = n0;
+    p->n1 = n1;
+    p->device = dry ? -1 : device;
+    p->flags = flags;
+    p->inverse = (flags & PIFFT_INVERSE) != 0;
+    DeviceGuard g(p->device);
+    if (build_matrix(p, dry)) {
+        std::string keep = g_err;
+        release(p);
+        g_err = keep;
+        return -1;
+    }
+    *out = p;
+    return 0;
+}
+
 const char* kRealOnly = "real plans (pifft_plan_create_real) run through pifft_execute_device, "
                         "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
+const char* kMatrixOnly = "matrix plans (pifft_plan_create_matrix) run through pifft_execute_device, "
+                          "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
+// why a host-boundary / multi-plan / tree / tuning entry point refuses plan p, or NULL
+const char* device_only(const pifft_plan* p) { return p->real ? kRealOnly : p->matrix ? kMatrixOnly : nullptr; }
 
 // One launch.  With events (e0, e1): hipExtLaunchKernel binds them to the
 // kernel's own dispatch (its start and end timestamps, what rocprofv3 reports
@@ -961,6 +1096,14 @@ int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hip
             e = go(args, 0);
             break;
         }
+        case STEP_TRANSPOSE: {
+            TransposeArgs a = s.xa;
+            a.in = src;
+            a.out = dst;
+            void* args[] = {&a};
+            e = go(args, 0);
+            break;
+        }
         default:
             return fail("bad step kind %d", s.kind);
     }
@@ -989,6 +1132,9 @@ int check_buffers(const pifft_plan* p, const void* d_in, void* d_out) {
     if (!p) return fail("plan is NULL");
     if (!d_in || !d_out) return fail("NULL device buffer");
     if (d_in == d_out) return fail("in-place execution is not supported (d_in == d_out)");
+    // k_transpose moves fp32 values in 16-B pairs (pifft_matrix.h): hipMalloc's alignment is enough
+    if (p->matrix && (((uintptr_t)d_in | (uintptr_t)d_out) & 15))
+        return fail("matrix plans need 16-byte aligned device buffers");
     return 0;
 }
 
@@ -1308,6 +1454,35 @@ int pifft_plan_dry_run_real(uint64_t n, uint32_t workers, uint32_t batch, int pr
 
 int pifft_plan_is_real(const pifft_plan* plan) { return plan ? plan->real : -1; }
 
+int pifft_plan_create_matrix(pifft_plan** plan, uint64_t n0, uint64_t n1, uint32_t batch, int prec, int device,
+                             int flags) {
+    return create_matrix(plan, n0, n1, batch, prec, device, flags);
+}
+
+int pifft_plan_dry_run_matrix(uint64_t n0, uint64_t n1, uint32_t batch, int prec, int flags, pifft_plan_info* info) {
+    if (!info) return fail("info is NULL");
+    pifft_plan* p = nullptr;
+    if (create_matrix(&p, n0, n1, batch, prec, -1, flags, true)) return -1;
+    const int rc = pifft_plan_get_info(p, info);
+    release(p);
+    return rc;
+}
+
+int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1) {
+    if (!plan || !n0 || !n1) return fail("NULL argument");
+    *n0 = plan->matrix ? plan->n0 : 1;
+    *n1 = plan->matrix ? plan->n1 : plan->real ? plan->real_n : plan->n;
+    return 0;
+}
+
+int pifft_plan_launch_grid(const pifft_plan* plan, int launch, uint32_t* workgroups) {
+    if (!plan || !workgroups) return fail("NULL argument");
+    if (launch < 0 || launch >= (int)plan->steps.size()) return fail("launch %d out of range", launch);
+    const dim3& g = plan->steps[(size_t)launch].grid;
+    *workgroups = g.x * g.y * g.z;
+    return 0;
+}
+
 int pifft_instance_count(void) { return (int)pass_kernels().size(); }
 
 int pifft_instance_desc(int i, int32_t* desc) {
@@ -1401,6 +1576,10 @@ int pifft_plan_get_info(const pifft_plan* p, pifft_plan_info* info) {
         info->in_elems = (uint64_t)p->batch * (p->real == 1 ? H : H + 1);
         info->out_elems = (uint64_t)p->batch * (p->real == 1 ? H + 1 : H);
         info->workspace_bytes += p->bytes_z + p->rtw_bytes;
+    }
+    if (p->matrix) {  // n = n0 n1 (the shape's); a row's length; Z on top of the one W and both chains' tables
+        info->local_n = p->n1;
+        info->workspace_bytes += p->bytes_z;
     }
     info->layout = (p->wil ? 1 : 0) | (p->ilv ? 2 : 0);
     info->num_launches = (int)p->steps.size();
@@ -1533,7 +1712,7 @@ int pifft_debug_wg_clock(pifft_plan* p, int launch, const void* d_in, void* d_ou
 int pifft_plan_tune_workspace(pifft_plan* p, const void* d_in, void* d_out, void* stream, int tries,
                               float* best_ms) {
     if (check_buffers(p, d_in, d_out)) return -1;
-    if (p->real) return fail("pifft_plan_tune_workspace: %s", kRealOnly);
+    if (device_only(p)) return fail("pifft_plan_tune_workspace: %s", device_only(p));
     if (tries < 1) return fail("tries must be >= 1");
     DeviceGuard g(p->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1666,7 +1845,7 @@ int pifft_execute_device_timed(pifft_plan* p, const void* d_in, void* d_out, voi
 }
 
 int pifft_execute(pifft_plan* p, const void* host_in, void* host_out, double* ms1, double* ms2) {
-    if (p && p->real) return fail("pifft_execute: %s", kRealOnly);
+    if (p && device_only(p)) return fail("pifft_execute: %s", device_only(p));
     return pifft_execute_group(&p, 1, host_in, host_out, ms1, ms2);
 }
 
@@ -1676,7 +1855,7 @@ int pifft_execute_group(pifft_plan** plans, int np, const void* host_in, void* h
     if (!host_in) return fail("host_in is NULL");
     for (int i = 0; i < np; i++) {
         if (!plans[i]) return fail("plan %d is NULL", i);
-        if (plans[i]->real) return fail("pifft_execute_group: %s", kRealOnly);
+        if (device_only(plans[i])) return fail("pifft_execute_group: %s", device_only(plans[i]));
         if (plans[i]->n != plans[0]->n || plans[i]->batch != plans[0]->batch ||
             plans[i]->prec != plans[0]->prec)
             return fail("plans of a group must share n, batch and precision");
@@ -1806,7 +1985,7 @@ int pifft_execute_group_kernel_times(pifft_plan** plans, int np, double* ms1, do
     if (!plans || np <= 0) return fail("no plans");
     for (int i = 0; i < np; i++) {
         if (!plans[i]) return fail("plan %d is NULL", i);
-        if (plans[i]->real) return fail("pifft_execute_group_kernel_times: %s", kRealOnly);
+        if (device_only(plans[i])) return fail("pifft_execute_group_kernel_times: %s", device_only(plans[i]));
         if (!plans[i]->d_hin || !plans[i]->d_hout) return fail("plan %d: no staged input (call pifft_execute_group first)", i);
     }
     for (int i = 0; i < np; i++) {
@@ -1855,13 +2034,13 @@ int pifft_interleave_device(const void* d_slices, void* d_out, uint64_t n, uint3
 int pifft_allgather(pifft_plan* const* plans, int nplans, const void* const* d_slices, void* const* d_natural,
                     double* ms) {
     for (int i = 0; plans && i < nplans; i++)
-        if (plans[i] && plans[i]->real) return fail("pifft_allgather: %s", kRealOnly);
+        if (plans[i] && device_only(plans[i])) return fail("pifft_allgather: %s", device_only(plans[i]));
     return gather_group(plans, nplans, d_slices, d_natural, ms);
 }
 
 int pifft_tree_device(pifft_plan* p, const void* d_in, void* d_seg, void* stream) {
     if (check_buffers(p, d_in, d_seg)) return -1;
-    if (p->real) return fail("pifft_tree_device: %s", kRealOnly);
+    if (device_only(p)) return fail("pifft_tree_device: %s", device_only(p));
     if (p->inverse) return fail("pifft_tree_device: forward plans only (the reference's tree)");
     DeviceGuard g(p->device);
     hipStream_t st = (hipStream_t)stream;  // NULL = the default stream

@@ -24,7 +24,8 @@ PROFILE_ALL, PROFILE_SAMPLED = 0, 1
 SEPARATE_TREE = 4  # flag bit: the tree never fused into the first pass (CLI -u)
 INVERSE = 8  # flag bit: the unnormalised inverse transform, e^{+2 pi i nk/N} (CLI -i)
 REAL_FORWARD, REAL_INVERSE = 0, 1  # pifft_plan_create_real directions: R2C, C2R
-KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r"}
+MATRIX_TRANSPOSED_OUT = 16  # flag bit of pifft_plan_create_matrix: the result left as batch arrays of n1 x n0
+KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r", 7: "transpose"}
 MAX_LAUNCH_INFO = 256  # PIFFT_MAX_LAUNCH_INFO (include/pifft.h)
 
 
@@ -82,6 +83,12 @@ _SIGS = {
     "pifft_plan_dry_run_real": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
                                                ctypes.c_int, ctypes.POINTER(PlanInfo)]),
     "pifft_plan_is_real": (ctypes.c_int, [_P]),
+    "pifft_plan_create_matrix": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pifft_plan_dry_run_matrix": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.POINTER(PlanInfo)]),
+    "pifft_plan_get_dims": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "pifft_plan_launch_grid": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
     "pifft_plan_kernel_name": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     "pifft_execute_device": (ctypes.c_int, [_P, _P, _P, _P]),
     "pifft_execute_device_timed": (ctypes.c_int, [_P, _P, _P, _P, ctypes.POINTER(ctypes.c_float),
@@ -221,6 +228,18 @@ class Plan:
         """pifft_plan_is_real: 0 a complex plan, 1 R2C, 2 C2R."""
         return lib().pifft_plan_is_real(self._h)
 
+    def dims(self) -> tuple[int, int]:
+        """pifft_plan_get_dims: (n0, n1) of a matrix plan, (1, n) of a 1-D or real plan."""
+        n0, n1 = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().pifft_plan_get_dims(self._h, ctypes.byref(n0), ctypes.byref(n1)), "pifft_plan_get_dims")
+        return n0.value, n1.value
+
+    def launch_grid(self, launch: int) -> int:
+        """pifft_plan_launch_grid: the workgroups of one launch."""
+        g = ctypes.c_uint32()
+        _check(lib().pifft_plan_launch_grid(self._h, launch, ctypes.byref(g)), "pifft_plan_launch_grid")
+        return g.value
+
     def kernel_name(self, launch: int) -> str:
         """Demangled kernel function of one launch (as rocprofv3 names it)."""
         buf = ctypes.create_string_buffer(512)
@@ -303,6 +322,49 @@ class RealPlan(Plan):
         h = _P()
         _check(lib().pifft_plan_create_real(ctypes.byref(h), n, workers, batch, prec, 0 if device is None else device,
                                             REAL_INVERSE if inverse else REAL_FORWARD), "pifft_plan_create_real")
+        self._h = h
+        self.info = self._info()
+
+
+def _matrix_flags(inverse: bool, transposed_out: bool) -> int:
+    return (INVERSE if inverse else 0) | (MATRIX_TRANSPOSED_OUT if transposed_out else 0)
+
+
+def _matrix_args(n0, n1, batch, prec) -> None:
+    """The binding's own checks: what ctypes would wrap silently into the C types."""
+    for name, v, bits in (("n0", n0, 64), ("n1", n1, 64), ("batch", batch, 32)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0 or v >> bits:
+            raise PifftError(f"{name} = {v!r} is not an unsigned {bits}-bit integer")
+    if prec not in (F32, F64):
+        raise PifftError("prec must be F32 or F64")
+
+
+def transpose_tile(prec: int) -> int:
+    """PIFFT_TRANSPOSE_TILE (include/pifft.h): T of the transpose kernel's
+    min(rows, T) x min(cols, T) tiles, 512 bytes of values."""
+    return 32 if prec == F64 else 64
+
+
+def transpose_tiles(rows: int, cols: int, batch: int, prec: int) -> int:
+    """Tiles (= workgroups, below the grid cap) of one transpose launch over
+    batch matrices of rows x cols values, by the rule of include/pifft.h."""
+    t = transpose_tile(prec)
+    return batch * (rows // min(rows, t)) * (cols // min(cols, t))
+
+
+class MatrixPlan(Plan):
+    """A 2-D complex transform of batch arrays of n0 x n1 values
+    (pifft_plan_create_matrix), unnormalised; inverse=True: e^{+...}, no
+    1/(n0 n1); transposed_out=True: the result left as arrays of n1 x n0.  Runs
+    through the device-boundary methods (execute_device, execute_device_timed,
+    profile_*, launch_loop), the others raise PifftError."""
+
+    def __init__(self, n0: int, n1: int, batch: int = 1, prec: int = F64, *, device: int | None = None,
+                 inverse: bool = False, transposed_out: bool = False):
+        _matrix_args(n0, n1, batch, prec)
+        h = _P()
+        _check(lib().pifft_plan_create_matrix(ctypes.byref(h), n0, n1, batch, prec, 0 if device is None else device,
+                                              _matrix_flags(inverse, transposed_out)), "pifft_plan_create_matrix")
         self._h = h
         self.info = self._info()
 
@@ -453,6 +515,16 @@ def dry_run_real(n: int, workers: int = 1, batch: int = 1, prec: int = F64, *, i
     info = PlanInfo()
     _check(lib().pifft_plan_dry_run_real(n, workers, batch, prec, REAL_INVERSE if inverse else REAL_FORWARD,
                                          ctypes.byref(info)), "pifft_plan_dry_run_real")
+    return describe_info(info)
+
+
+def dry_run_matrix(n0: int, n1: int, batch: int = 1, prec: int = F64, *, inverse: bool = False,
+                   transposed_out: bool = False) -> dict:
+    """The matrix plan that would be built (pifft_plan_dry_run_matrix), without a device."""
+    _matrix_args(n0, n1, batch, prec)
+    info = PlanInfo()
+    _check(lib().pifft_plan_dry_run_matrix(n0, n1, batch, prec, _matrix_flags(inverse, transposed_out),
+                                           ctypes.byref(info)), "pifft_plan_dry_run_matrix")
     return describe_info(info)
 
 

@@ -121,7 +121,8 @@ typedef struct pifft_plan_info {
     uint64_t launch_bytes[PIFFT_MAX_LAUNCH_INFO]; /* algorithmic bytes of each launch
                                   (read+write of the data, twiddle tables excluded) */
     int32_t launch_kind[PIFFT_MAX_LAUNCH_INFO]; /* 1 tree, 2 pass, 3 interleave, 4 tree fused
-                                  into a pass, 5 / 6 the R2C / C2R fix-up of a real plan */
+                                  into a pass, 5 / 6 the R2C / C2R fix-up of a real plan,
+                                  7 a transpose of a matrix plan */
     int32_t launch_fn[PIFFT_MAX_LAUNCH_INFO]; /* kernel of each launch: launches with the same id
                                   run the same kernel function (ids 0, 1, ... in order
                                   of first use) -- what rocprof aggregates per kernel */
@@ -218,6 +219,65 @@ int pifft_plan_create_real(pifft_plan** plan, uint64_t n, uint32_t workers, uint
 int pifft_plan_dry_run_real(uint64_t n, uint32_t workers, uint32_t batch, int prec,
                             int direction, pifft_plan_info* info);
 int pifft_plan_is_real(const pifft_plan* plan);
+
+/* 2-D complex transforms: batch row-major arrays of n0 rows x n1 columns, n1
+ * contiguous, n0 and n1 powers of two >= 2 (they need not be equal),
+ *   X[k0][k1] = sum_{j0,j1} x[j0][j1] e^{-2 pi i (j0 k0/n0 + j1 k1/n1)},
+ * unnormalised; with PIFFT_INVERSE e^{+...} and no 1/(n0 n1).  batch *
+ * max(n0, n1) must fit 32 bits.  d_in != d_out, d_in is never written, and both
+ * are 16-byte aligned (hipMalloc's alignment is enough).
+ *
+ * A matrix plan is the two 1-D plans pifft_plan_dry_run describes for the rows,
+ * (n1, 1 worker, batch*n0), and the columns, (n0, 1 worker, batch*n1) --
+ * natural order, launch for launch, PIFFT_INVERSE on both for an inverse plan
+ * -- with tiled transposes (launch_kind 7, k_transpose) between them over a
+ * plan-owned staging buffer Z of batch*n0*n1 values:
+ *   flags 0:  rows d_in -> Z, transpose Z -> d_out, columns d_out -> Z,
+ *             transpose Z -> d_out;
+ *   PIFFT_MATRIX_TRANSPOSED_OUT: rows d_in -> d_out, transpose d_out -> Z,
+ *             columns Z -> d_out.  The result stays transposed, batch arrays of
+ *             n1 x n0: out[b][k1][k0].  One launch and 2 n0 n1 values of traffic
+ *             less; for callers that multiply pointwise and transform back (an
+ *             inverse plan of the n1 x n0 shape with the same flag returns the
+ *             original layout).
+ * The result equals the composition of the two 1-D plans around an exact
+ * transpose bit for bit.  The plan owns Z, one ping-pong workspace (the larger
+ * of the two chains') and both chains' tables: workspace_bytes.
+ *
+ * The transpose kernel moves one tile of t_r x t_c values per workgroup,
+ * t_r = min(rows, T), t_c = min(cols, T) with T = PIFFT_TRANSPOSE_TILE(prec)
+ * (512 bytes of values), rows x cols the launch's input matrices: (rows / t_r) *
+ * (cols / t_c) * batch tiles, one workgroup each up to the grid cap of 262144
+ * (PIFFT_STRIDE_GRID_MAX under PIFFT_TUNING=1 lowers it), walked grid-stride.
+ *
+ * The info of a matrix plan: n = n0*n1, workers = num_workers = 1, local_n =
+ * n1, in_elems = out_elems = batch*n0*n1, tree_launches 0, num_passes and
+ * radix / lines / vpt the rows' passes then the columns', launch_kind /
+ * launch_bytes / launch_mode the two inner plans' entries with the transposes
+ * (kind 7, mode 0, 2*batch*n0*n1 elements read plus written) between them,
+ * layout the OR of the inner plans'.  A plan of more than 8 passes in all is
+ * refused (none below 2^28 per axis).
+ *
+ * A matrix plan runs through the entry points a real plan runs through
+ * (execute_device, execute_device_timed, profile_start / profile_read,
+ * launch_loop, plan_get_info, plan_kernel_name, plan_destroy) and the two
+ * getters below; the host-boundary and multi-plan entry points, tree_device
+ * and plan_tune_workspace return -1 on it, and pifft_plan_is_real 0.  The 1-D
+ * entry points keep refusing flag 16. */
+#define PIFFT_MATRIX_TRANSPOSED_OUT 16
+#define PIFFT_TRANSPOSE_TILE(prec) ((prec) == PIFFT_F64 ? 32 : 64)
+int pifft_plan_create_matrix(pifft_plan** plan, uint64_t n0, uint64_t n1, uint32_t batch,
+                             int prec, int device, int flags);
+int pifft_plan_dry_run_matrix(uint64_t n0, uint64_t n1, uint32_t batch, int prec, int flags,
+                              pifft_plan_info* info);
+
+/* The dimensions a plan was made for: (n0, n1) of a matrix plan; n0 = 1 and
+ * n1 = info.n for 1-D and real plans. */
+int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1);
+
+/* The grid of launch `launch` (< info.num_launches) in workgroups, for any plan
+ * (beside pifft_plan_kernel_name). */
+int pifft_plan_launch_grid(const pifft_plan* plan, int launch, uint32_t* workgroups);
 
 /* Diagnostics (no reference counterpart): the registry of compiled k_pass
  * instances, and which of them a plan would launch.  pifft_instance_desc
