@@ -10,6 +10,7 @@
 //   [interleave: slice-major -> natural order, whole transform on one GPU]
 //   [real plans: the N/2-point chain above plus one fix-up launch (create_real, pifft_real.h)]
 //   [matrix plans: two such chains, rows and columns, with transposes between them (create_matrix, pifft_matrix.h)]
+//   [chirp plans: any length N, two chains of M >= 2N - 1 around a pointwise product (create_chirp, pifft_chirp.h)]
 //
 // Buffers ping-pong between the caller's output and one plan-owned workspace.
 // Twiddles are host-built tables in HBM (w_R per pass, two-level w_M and w_N;
@@ -18,6 +19,7 @@
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE  // sincos (reference_omega_levels)
 #endif
+#include "pifft_chirp.h"
 #include "pifft_gather.h"
 #include "pifft_kernels.h"
 #include "pifft_matrix.h"
@@ -260,16 +262,18 @@ const void* find_aux_twin(const void* fn, int sw) {
 // plan
 // ---------------------------------------------------------------------------
 enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, STEP_R2C_POST = 5, STEP_C2R_PRE = 6,
-       STEP_TRANSPOSE = 7 };
+       STEP_TRANSPOSE = 7, STEP_CHIRP_PRE = 8, STEP_SPECTRUM_MUL = 9, STEP_CHIRP_POST = 10 };
 // BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real); a
-// matrix plan's, batch x n0 x n1 values (build_matrix)
-enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, NBUF = 5 };
+// matrix plan's, batch x n0 x n1 values (build_matrix); a chirp plan's Z, and
+// BUF_Y its Y, batch x M values each (build_chirp)
+enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, BUF_Y = 5, NBUF = 6 };
 
 // a step's twiddle tables as byte offsets into the plan's blob (kNoTable:
 // none); materialise resolves them into pa / ta / ra once, launch_step never
 constexpr size_t kNoTable = (size_t)-1;
 struct StepTables {
-    size_t r = kNoTable, lo = kNoTable, hi = kNoTable;  // a pass's w_R and two-level w_M; a real step's two-level w_N
+    // a pass's w_R and two-level w_M; a real step's two-level w_N; a chirp step's two-level w_2N
+    size_t r = kNoTable, lo = kNoTable, hi = kNoTable;
     size_t tree_direct = kNoTable, tree_lo = kNoTable, tree_hi = kNoTable;  // TreeTw
 };
 
@@ -288,6 +292,7 @@ struct Step {
     uint32_t il_log_n = 0, il_log_p = 0;
     RealArgs ra{};  // STEP_R2C_POST / STEP_C2R_PRE
     TransposeArgs xa{};  // STEP_TRANSPOSE
+    ChirpArgs ca{};  // STEP_CHIRP_PRE / STEP_SPECTRUM_MUL / STEP_CHIRP_POST
     StepTables tab;
     uint64_t bytes = 0;
 };
@@ -310,6 +315,13 @@ struct pifft_plan : pifft::PlanShape {  // (the shape it was planned for, pifft_
     // the row and the column chain (build_matrix)
     bool matrix = false;
     uint64_t n0 = 0, n1 = 0;
+    // pifft_plan_create_chirp: batch rows of chirp_n values, chirp_n no power
+    // of two.  The shape above is (M, one worker, batch), M = chirp_length;
+    // steps, tables and W are those of the forward and the inverse chain of M
+    // (build_chirp); d_bt: Bt = DFT_M(b) / M, M values
+    uint64_t chirp_n = 0;
+    size_t bytes_y = 0, bytes_bt = 0;
+    void* d_bt = nullptr;
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -439,6 +451,16 @@ TwoLevel two_level(TableBuilder& tb, uint64_t L) {
     return t;
 }
 
+// the same for an L that is no power of two (a chirp plan's w_2N): 2^h ~ sqrt L
+// entries of w_L^e, then ceil(L / 2^h) of w_L^(e 2^h)
+TwoLevel two_level_any(TableBuilder& tb, uint64_t L) {
+    TwoLevel t;
+    t.h = (uint32_t)((ilog2u(L - 1) + 2) / 2);
+    t.lo = tb.roots(L, 1ull << t.h, 1);
+    t.hi = tb.roots(L, (L + (1ull << t.h) - 1) >> t.h, 1ull << t.h);
+    return t;
+}
+
 // slice-major -> natural order: k_interleave_tile (LDS tile of all P slices,
 // P <= 2048) from P = 2^5 at fp64 and P = 2 at fp32, else k_interleave (one
 // thread per output element, any P); profiles/r02_interleave_ab.log
@@ -459,6 +481,7 @@ void release(pifft_plan* p) {
     for (int b = BUF_W; b < NBUF; b++)
         if (p->buf[b]) (void)hipFree(p->buf[b]);
     if (p->d_tw) (void)hipFree(p->d_tw);
+    if (p->d_bt) (void)hipFree(p->d_bt);
     if (p->d_hin) (void)hipFree(p->d_hin);
     if (p->d_hout) (void)hipFree(p->d_hout);
     if (p->d_gather) (void)hipFree(p->d_gather);
@@ -758,10 +781,15 @@ void add_real_step(pifft_plan* p, TableBuilder& tb, uint64_t n, bool c2r) {
 // events, and the LDS attribute of the kernels the final steps launch.
 int materialise(pifft_plan* p, const TableBuilder& tb) {
     HIPCHK(hipMalloc(&p->d_tw, p->tw_bytes + p->rtw_bytes));
+    if (p->bytes_bt) HIPCHK(hipMalloc(&p->d_bt, p->bytes_bt));
     if (!tb.blob.empty()) HIPCHK(hipMemcpy(p->d_tw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
     auto at = [&](size_t off) { return off == kNoTable ? nullptr : (const void*)((const char*)p->d_tw + off); };
     auto resolve = [&](Step& s) {
         if (s.kind == STEP_TRANSPOSE) return;  // (no table, static LDS)
+        if (s.kind >= STEP_CHIRP_PRE) {
+            s.ca.tw_lo = at(s.tab.lo), s.ca.tw_hi = at(s.tab.hi), s.ca.bt = p->d_bt;
+            return;
+        }
         TreeTw& tree = s.kind == STEP_TREE ? s.ta.tw : s.pa.tree;
         tree.direct = at(s.tab.tree_direct), tree.lo = at(s.tab.tree_lo), tree.hi = at(s.tab.tree_hi);
         if (s.kind == STEP_R2C_POST || s.kind == STEP_C2R_PRE) s.ra.tw_lo = at(s.tab.lo), s.ra.tw_hi = at(s.tab.hi);
@@ -778,6 +806,7 @@ int materialise(pifft_plan* p, const TableBuilder& tb) {
                        : hipMalloc(&p->buf[BUF_W], p->bytes_w));
     if (p->bytes_ta) HIPCHK(hipMalloc(&p->buf[BUF_TA], p->bytes_ta));
     if (p->bytes_z) HIPCHK(hipMalloc(&p->buf[BUF_Z], p->bytes_z));
+    if (p->bytes_y) HIPCHK(hipMalloc(&p->buf[BUF_Y], p->bytes_y));
     HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     p->ev.resize(2 * p->steps.size());
     for (auto& e : p->ev) HIPCHK(hipEventCreateWithFlags(&e, kTimingEventFlags));
@@ -923,6 +952,23 @@ int create_real(pifft_plan** out, uint64_t n, uint32_t workers, uint32_t batch, 
                           PIFFT_OUT_NATURAL | (c2r ? PIFFT_INVERSE : 0), dry, n);
 }
 
+// a chain's launches joined to plan p with its caller-side buffers renamed
+// (matrix and chirp plans: two chains planned by plan_chain over one builder)
+void splice(pifft_plan* p, const pifft_plan& q, int in, int out) {
+    for (Step s : q.steps) {
+        s.src = s.src == BUF_IN ? in : s.src == BUF_OUT ? out : s.src;
+        s.dst = s.dst == BUF_OUT ? out : s.dst;
+        p->steps.push_back(s);
+    }
+    for (int i = 0; i < q.npasses; i++) {
+        p->radix[p->npasses] = q.radix[i];
+        p->lines[p->npasses] = q.lines[i];
+        p->vpt[p->npasses++] = q.vpt[i];
+    }
+    p->wil |= q.wil;
+    p->ilv |= q.ilv;
+}
+
 // Matrix plans (pifft_plan_create_matrix; the kernel in pifft_matrix.h): batch
 // arrays of n0 x n1 values.  The plan is the two complex plans plan_chain makes
 // for the rows, (n1, one worker, batch n0), and the columns, (n0, one worker,
@@ -956,21 +1002,6 @@ int build_matrix(pifft_plan* p, bool dry) {
     const uint64_t total = (uint64_t)p->batch * p->n0 * p->n1;
     p->bytes_z = (size_t)total * p->esz;
     p->bytes_w = std::max(chain[0].bytes_w, chain[1].bytes_w);
-    // a chain's launches with its caller-side buffers renamed
-    auto splice = [&](const pifft_plan& q, int in, int out) {
-        for (Step s : q.steps) {
-            s.src = s.src == BUF_IN ? in : s.src == BUF_OUT ? out : s.src;
-            s.dst = s.dst == BUF_OUT ? out : s.dst;
-            p->steps.push_back(s);
-        }
-        for (int i = 0; i < q.npasses; i++) {
-            p->radix[p->npasses] = q.radix[i];
-            p->lines[p->npasses] = q.lines[i];
-            p->vpt[p->npasses++] = q.vpt[i];
-        }
-        p->wil |= q.wil;
-        p->ilv |= q.ilv;
-    };
     auto transpose = [&](uint64_t rows, uint64_t cols, int src, int dst) {
         Step s;
         s.kind = STEP_TRANSPOSE;
@@ -985,13 +1016,13 @@ int build_matrix(pifft_plan* p, bool dry) {
         p->steps.push_back(s);
     };
     if (tout) {
-        splice(chain[0], BUF_IN, BUF_OUT);
+        splice(p, chain[0], BUF_IN, BUF_OUT);
         transpose(p->n0, p->n1, BUF_OUT, BUF_Z);
-        splice(chain[1], BUF_Z, BUF_OUT);
+        splice(p, chain[1], BUF_Z, BUF_OUT);
     } else {
-        splice(chain[0], BUF_IN, BUF_Z);
+        splice(p, chain[0], BUF_IN, BUF_Z);
         transpose(p->n0, p->n1, BUF_Z, BUF_OUT);
-        splice(chain[1], BUF_OUT, BUF_Z);
+        splice(p, chain[1], BUF_OUT, BUF_Z);
         transpose(p->n1, p->n0, BUF_Z, BUF_OUT);
     }
     return dry ? 0 : materialise(p, tb);
@@ -1034,12 +1065,107 @@ int create_matrix(pifft_plan** out, uint64_t n0, uint64_t n1, uint32_t batch, in
     return 0;
 }
 
+// Chirp plans (pifft_plan_create_chirp; kernels and formulas in pifft_chirp.h):
+// batch rows of N values, N no power of two.  The plan is the two complex
+// plans plan_chain makes for (M, one worker, natural order, batch), M =
+// chirp_length(N) -- untouched; the second with PIFFT_INVERSE -- around a
+// pointwise product, between two streaming launches, over Z (BUF_Z) and Y
+// (BUF_Y), batch x M values each:
+//   [k_chirp_pre: d_in -> Z] [forward chain: Z -> Y] [k_spectrum_mul: Y in place]
+//   [inverse chain: Y -> Z] [k_chirp_post: Z -> d_out]
+// A chain keeps its own ping-pong (splice, as build_matrix) and W as ever; the
+// chains never run concurrently: one W of the larger size.  Both chains'
+// tables and the two-level table of w_2N go into one blob.  The plan's own
+// PIFFT_INVERSE is the swapping twins of the first and the last launch; the
+// chains between are the same in both directions.
+int chirp_spectrum(pifft_plan* p);  // (below: it runs a plan)
+int build_chirp(pifft_plan* p, bool dry) {
+    const uint64_t N = p->chirp_n, M = p->n;
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    pifft_plan chain[2];  // forward, inverse: planned here, never materialised (they own nothing)
+    for (int c = 0; c < 2; c++) {
+        pifft_plan& q = chain[c];
+        static_cast<PlanShape&>(q) = plan_shape(M, 1, 0, 1, p->batch, p->prec, true, false, false);
+        q.device = -1;
+        q.flags = c ? PIFFT_INVERSE : 0;
+        q.inverse = c == 1;
+        if (plan_chain(&q, tb)) return -1;
+    }
+    const TwoLevel tw = two_level_any(tb, 2 * N);
+    tb.align();
+    p->tw_bytes = tb.size();
+    if (chain[0].npasses + chain[1].npasses > 8)
+        return fail("chirp plan: %d + %d passes exceed the 8 a plan describes", chain[0].npasses, chain[1].npasses);
+    p->bytes_z = p->bytes_y = (size_t)p->batch * M * p->esz;
+    p->bytes_bt = (size_t)M * p->esz;
+    p->bytes_w = std::max(chain[0].bytes_w, chain[1].bytes_w);
+    auto stream = [&](int step, int kind, int sw, int src, int dst, uint64_t elems) {
+        Step s;
+        s.kind = step;
+        s.fn = chirp_fn(kind, p->prec, sw);
+        const uint64_t units = p->prec == PIFFT_F64 ? chirp_units<double>(kind, N, M) : chirp_units<float>(kind, N, M);
+        s.block = dim3(256);
+        s.grid = dim3(stride_grid((uint64_t)p->batch * units));
+        s.ca = p->prec == PIFFT_F64 ? chirp_args<double>(kind, N, p->batch, (uint64_t)s.grid.x * 256)
+                                    : chirp_args<float>(kind, N, p->batch, (uint64_t)s.grid.x * 256);
+        s.ca.tw_h = tw.h;
+        s.tab.lo = tw.lo;
+        s.tab.hi = tw.hi;
+        s.src = src;
+        s.dst = dst;
+        s.bytes = elems * p->esz;
+        p->steps.push_back(s);
+    };
+    stream(STEP_CHIRP_PRE, CHIRP_PRE, p->inverse ? 1 : 0, BUF_IN, BUF_Z, (uint64_t)p->batch * (N + M));
+    splice(p, chain[0], BUF_Z, BUF_Y);
+    stream(STEP_SPECTRUM_MUL, CHIRP_MUL, 0, BUF_Y, BUF_Y, (uint64_t)p->batch * 2 * M + M);
+    splice(p, chain[1], BUF_Y, BUF_Z);
+    stream(STEP_CHIRP_POST, CHIRP_POST, p->inverse ? 2 : 0, BUF_Z, BUF_OUT, (uint64_t)p->batch * 2 * N);
+    return dry ? 0 : (materialise(p, tb) || chirp_spectrum(p)) ? -1 : 0;
+}
+
+int create_chirp(pifft_plan** out, uint64_t n, uint32_t batch, int prec, int device, int flags, bool dry = false) {
+    if (!out) return fail("plan pointer is NULL");
+    *out = nullptr;
+    if (n >= 2 && is_pow2(n))
+        return fail("Invalid input size (a chirp plan takes an n that is no power of two: use pifft_plan_create for 2^i)");
+    if (n < 3 || n > (1ull << 27)) return fail("Invalid input size (a chirp plan needs 3 <= n <= 2^27)");
+    if (batch == 0) return fail("batch must be >= 1");
+    if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
+    if (flags & ~PIFFT_INVERSE) return fail("unknown flags %d (a chirp plan takes PIFFT_INVERSE)", flags);
+    if (!dry) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available");
+        if (device < 0 || device >= ndev) return fail("device %d out of range (%d devices)", device, ndev);
+    }
+    pifft_plan* p = new pifft_plan;
+    static_cast<PlanShape&>(*p) = plan_shape(chirp_length(n), 1, 0, 1, batch, prec, true, false, false);
+    p->chirp_n = n;
+    p->device = dry ? -1 : device;
+    p->flags = flags;
+    p->inverse = (flags & PIFFT_INVERSE) != 0;
+    DeviceGuard g(p->device);
+    if (build_chirp(p, dry)) {
+        std::string keep = g_err;
+        release(p);
+        g_err = keep;
+        return -1;
+    }
+    *out = p;
+    return 0;
+}
+
 const char* kRealOnly = "real plans (pifft_plan_create_real) run through pifft_execute_device, "
                         "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
 const char* kMatrixOnly = "matrix plans (pifft_plan_create_matrix) run through pifft_execute_device, "
                           "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
+const char* kChirpOnly = "chirp plans (pifft_plan_create_chirp) run through pifft_execute_device, "
+                         "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
 // why a host-boundary / multi-plan / tree / tuning entry point refuses plan p, or NULL
-const char* device_only(const pifft_plan* p) { return p->real ? kRealOnly : p->matrix ? kMatrixOnly : nullptr; }
+const char* device_only(const pifft_plan* p) {
+    return p->real ? kRealOnly : p->matrix ? kMatrixOnly : p->chirp_n ? kChirpOnly : nullptr;
+}
 
 // One launch.  With events (e0, e1): hipExtLaunchKernel binds them to the
 // kernel's own dispatch (its start and end timestamps, what rocprofv3 reports
@@ -1049,7 +1175,7 @@ const char* device_only(const pifft_plan* p) { return p->real ? kRealOnly : p->m
 // (round-2 verdict); kernel-bound events add nothing to the stream.
 int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hipStream_t st,
                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    void* base[NBUF] = {const_cast<void*>(d_in), d_out, p->buf[BUF_W], p->buf[BUF_TA], p->buf[BUF_Z]};
+    void* base[NBUF] = {const_cast<void*>(d_in), d_out, p->buf[BUF_W], p->buf[BUF_TA], p->buf[BUF_Z], p->buf[BUF_Y]};
     const char* src = (const char*)base[s.src] + s.src_off * p->esz;
     char* dst = (char*)base[s.dst] + s.dst_off * p->esz;
     auto go = [&](void** args, size_t lds) {
@@ -1104,6 +1230,16 @@ int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hip
             e = go(args, 0);
             break;
         }
+        case STEP_CHIRP_PRE:
+        case STEP_SPECTRUM_MUL:
+        case STEP_CHIRP_POST: {
+            ChirpArgs a = s.ca;
+            a.in = src;
+            a.out = dst;
+            void* args[] = {&a};
+            e = go(args, 0);
+            break;
+        }
         default:
             return fail("bad step kind %d", s.kind);
     }
@@ -1117,6 +1253,51 @@ int launch_steps(pifft_plan* p, const void* d_in, void* d_out, hipStream_t st, h
         if (launch_step(p, p->steps[i], d_in, d_out, st, ev ? ev[2 * i] : nullptr, ev ? ev[2 * i + 1] : nullptr))
             return -1;
     return 0;
+}
+
+// A chirp plan's Bt = DFT_M(b) / M, fixed at creation and the same for both
+// precisions up to its one final rounding: b is filled on the device in fp64
+// (k_chirp_fill, from an fp64 two-level table of w_2N), transformed by a
+// temporary fp64 plan of (M, one worker, batch 1), scaled by the exact 1/M and
+// rounded once to the plan's precision (k_chirp_bt).  No host sincos per
+// element, no host FFT.  Synchronous; everything but Bt is freed on return.
+int chirp_spectrum(pifft_plan* p) {
+    const uint64_t N = p->chirp_n, M = p->n;
+    TableBuilder tb(16);
+    const TwoLevel tw = two_level_any(tb, 2 * N);
+    pifft_plan* t = nullptr;
+    void *d_tab = nullptr, *d_b = nullptr, *d_B = nullptr;
+    auto run = [&]() -> int {
+        if (create(&t, M, 1, 0, 1, 1, PIFFT_F64, p->device, PIFFT_OUT_NATURAL)) return -1;
+        HIPCHK(hipMalloc(&d_tab, tb.blob.size()));
+        HIPCHK(hipMalloc(&d_b, (size_t)M * 16));
+        HIPCHK(hipMalloc(&d_B, (size_t)M * 16));
+        HIPCHK(hipMemcpy(d_tab, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
+        const dim3 grid(stride_grid(M)), block(256);
+        ChirpArgs a = chirp_args<double>(CHIRP_FILL, N, 1, (uint64_t)grid.x * 256);
+        a.out = d_b;
+        a.tw_lo = (const char*)d_tab + tw.lo;
+        a.tw_hi = (const char*)d_tab + tw.hi;
+        a.tw_h = tw.h;
+        void* fill_args[] = {&a};
+        HIPCHK(hipLaunchKernel(chirp_fn(CHIRP_FILL, 64, 0), grid, block, fill_args, 0, p->stream));
+        if (launch_steps(t, d_b, d_B, p->stream, nullptr)) return -1;
+        double inv_m = 1.0 / (double)M;
+        uint64_t m = M;
+        void* bt_args[] = {&d_B, &p->d_bt, &inv_m, &m};
+        HIPCHK(hipLaunchKernel(chirp_fn(CHIRP_BT, p->prec, 0), grid, block, bt_args, 0, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        return 0;
+    };
+    const int rc = run();
+    const std::string keep = g_err;
+    if (rc) (void)hipStreamSynchronize(p->stream);
+    if (d_tab) (void)hipFree(d_tab);
+    if (d_b) (void)hipFree(d_b);
+    if (d_B) (void)hipFree(d_B);
+    release(t);
+    g_err = keep;
+    return rc;
 }
 
 // per-launch durations of one recorded execution (ev as launch_steps)
@@ -1468,10 +1649,25 @@ int pifft_plan_dry_run_matrix(uint64_t n0, uint64_t n1, uint32_t batch, int prec
     return rc;
 }
 
+int pifft_plan_create_chirp(pifft_plan** plan, uint64_t n, uint32_t batch, int prec, int device, int flags) {
+    return create_chirp(plan, n, batch, prec, device, flags);
+}
+
+int pifft_plan_dry_run_chirp(uint64_t n, uint32_t batch, int prec, int flags, pifft_plan_info* info) {
+    if (!info) return fail("info is NULL");
+    pifft_plan* p = nullptr;
+    if (create_chirp(&p, n, batch, prec, -1, flags, true)) return -1;
+    const int rc = pifft_plan_get_info(p, info);
+    release(p);
+    return rc;
+}
+
+int pifft_plan_is_chirp(const pifft_plan* plan) { return plan ? (plan->chirp_n ? 1 : 0) : -1; }
+
 int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1) {
     if (!plan || !n0 || !n1) return fail("NULL argument");
     *n0 = plan->matrix ? plan->n0 : 1;
-    *n1 = plan->matrix ? plan->n1 : plan->real ? plan->real_n : plan->n;
+    *n1 = plan->matrix ? plan->n1 : plan->real ? plan->real_n : plan->chirp_n ? plan->chirp_n : plan->n;
     return 0;
 }
 
@@ -1580,6 +1776,11 @@ int pifft_plan_get_info(const pifft_plan* p, pifft_plan_info* info) {
     if (p->matrix) {  // n = n0 n1 (the shape's); a row's length; Z on top of the one W and both chains' tables
         info->local_n = p->n1;
         info->workspace_bytes += p->bytes_z;
+    }
+    if (p->chirp_n) {  // n = N; the chains' length M; Z, Y and Bt on top of the one W and all the tables
+        info->n = p->chirp_n;
+        info->in_elems = info->out_elems = (uint64_t)p->batch * p->chirp_n;
+        info->workspace_bytes += p->bytes_z + p->bytes_y + p->bytes_bt;
     }
     info->layout = (p->wil ? 1 : 0) | (p->ilv ? 2 : 0);
     info->num_launches = (int)p->steps.size();

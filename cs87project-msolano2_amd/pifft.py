@@ -25,7 +25,8 @@ SEPARATE_TREE = 4  # flag bit: the tree never fused into the first pass (CLI -u)
 INVERSE = 8  # flag bit: the unnormalised inverse transform, e^{+2 pi i nk/N} (CLI -i)
 REAL_FORWARD, REAL_INVERSE = 0, 1  # pifft_plan_create_real directions: R2C, C2R
 MATRIX_TRANSPOSED_OUT = 16  # flag bit of pifft_plan_create_matrix: the result left as batch arrays of n1 x n0
-KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r", 7: "transpose"}
+KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r", 7: "transpose",
+              8: "chirp_pre", 9: "spectrum_mul", 10: "chirp_post"}
 MAX_LAUNCH_INFO = 256  # PIFFT_MAX_LAUNCH_INFO (include/pifft.h)
 
 
@@ -87,6 +88,11 @@ _SIGS = {
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "pifft_plan_dry_run_matrix": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
                                                  ctypes.c_int, ctypes.POINTER(PlanInfo)]),
+    "pifft_plan_create_chirp": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int]),
+    "pifft_plan_dry_run_chirp": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(PlanInfo)]),
+    "pifft_plan_is_chirp": (ctypes.c_int, [_P]),
     "pifft_plan_get_dims": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "pifft_plan_launch_grid": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
     "pifft_plan_kernel_name": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
@@ -228,8 +234,12 @@ class Plan:
         """pifft_plan_is_real: 0 a complex plan, 1 R2C, 2 C2R."""
         return lib().pifft_plan_is_real(self._h)
 
+    def is_chirp(self) -> int:
+        """pifft_plan_is_chirp: 1 a chirp plan, else 0."""
+        return lib().pifft_plan_is_chirp(self._h)
+
     def dims(self) -> tuple[int, int]:
-        """pifft_plan_get_dims: (n0, n1) of a matrix plan, (1, n) of a 1-D or real plan."""
+        """pifft_plan_get_dims: (n0, n1) of a matrix plan, (1, n) of a 1-D, real or chirp plan."""
         n0, n1 = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().pifft_plan_get_dims(self._h, ctypes.byref(n0), ctypes.byref(n1)), "pifft_plan_get_dims")
         return n0.value, n1.value
@@ -369,6 +379,45 @@ class MatrixPlan(Plan):
         self.info = self._info()
 
 
+def _chirp_args(n, batch, prec) -> None:
+    """The binding's own checks: what ctypes would wrap silently into the C types."""
+    for name, v, bits in (("n", n, 64), ("batch", batch, 32)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0 or v >> bits:
+            raise PifftError(f"{name} = {v!r} is not an unsigned {bits}-bit integer")
+    if prec not in (F32, F64):
+        raise PifftError("prec must be F32 or F64")
+
+
+def chirp_length(n: int) -> int:
+    """M of a chirp plan of n values: the smallest power of two >= 2n - 1."""
+    return 1 << (2 * n - 2).bit_length()
+
+
+class ChirpPlan(Plan):
+    """A 1-D complex transform of batch rows of n values, n not a power of two
+    (pifft_plan_create_chirp: Bluestein's chirp-z algorithm on two chains of
+    chirp_length(n) values), unnormalised; inverse=True: e^{+...}, no 1/n.  Runs
+    through the device-boundary methods (execute_device, execute_device_timed,
+    profile_*, launch_loop), the others raise PifftError."""
+
+    def __init__(self, n: int, batch: int = 1, prec: int = F64, *, inverse: bool = False, device: int | None = None):
+        _chirp_args(n, batch, prec)
+        h = _P()
+        _check(lib().pifft_plan_create_chirp(ctypes.byref(h), n, batch, prec, 0 if device is None else device,
+                                             INVERSE if inverse else 0), "pifft_plan_create_chirp")
+        self._h = h
+        self.info = self._info()
+
+
+def plan_1d(n: int, batch: int = 1, prec: int = F64, *, inverse: bool = False, device: int | None = None) -> Plan:
+    """The whole 1-D transform of batch rows of n values on one device: Plan
+    (one worker, natural order) for a power of two, ChirpPlan otherwise -- the
+    dispatch pifft_plan_create_chirp leaves to its caller."""
+    if n >= 2 and n & (n - 1) == 0:
+        return Plan(n, 1, batch, prec, device=0 if device is None else device, inverse=inverse)
+    return ChirpPlan(n, batch, prec, inverse=inverse, device=device)
+
+
 def _real_kind(i: PlanInfo) -> int:
     kinds = i.launch_kind[: min(i.num_launches, MAX_LAUNCH_INFO)]
     return 1 if 5 in kinds else 2 if 6 in kinds else 0
@@ -390,6 +439,7 @@ def describe_info(i: PlanInfo) -> dict:
         "worker_interleaved": bool(i.layout & 1), "natural_store": bool(i.layout & 2),
         "inverse": bool(i.flags & INVERSE),
         "real": _real_kind(i),  # 0 complex, 1 R2C, 2 C2R (pifft_plan_is_real)
+        "chirp": 8 in i.launch_kind[: min(nl, MAX_LAUNCH_INFO)],  # a chirp plan (pifft_plan_is_chirp)
     }
 
 
@@ -525,6 +575,15 @@ def dry_run_matrix(n0: int, n1: int, batch: int = 1, prec: int = F64, *, inverse
     info = PlanInfo()
     _check(lib().pifft_plan_dry_run_matrix(n0, n1, batch, prec, _matrix_flags(inverse, transposed_out),
                                            ctypes.byref(info)), "pifft_plan_dry_run_matrix")
+    return describe_info(info)
+
+
+def dry_run_chirp(n: int, batch: int = 1, prec: int = F64, *, inverse: bool = False) -> dict:
+    """The chirp plan that would be built (pifft_plan_dry_run_chirp), without a device."""
+    _chirp_args(n, batch, prec)
+    info = PlanInfo()
+    _check(lib().pifft_plan_dry_run_chirp(n, batch, prec, INVERSE if inverse else 0, ctypes.byref(info)),
+           "pifft_plan_dry_run_chirp")
     return describe_info(info)
 
 

@@ -122,7 +122,8 @@ typedef struct pifft_plan_info {
                                   (read+write of the data, twiddle tables excluded) */
     int32_t launch_kind[PIFFT_MAX_LAUNCH_INFO]; /* 1 tree, 2 pass, 3 interleave, 4 tree fused
                                   into a pass, 5 / 6 the R2C / C2R fix-up of a real plan,
-                                  7 a transpose of a matrix plan */
+                                  7 a transpose of a matrix plan, 8 / 9 / 10 the chirp pre,
+                                  spectrum multiply and chirp post of a chirp plan */
     int32_t launch_fn[PIFFT_MAX_LAUNCH_INFO]; /* kernel of each launch: launches with the same id
                                   run the same kernel function (ids 0, 1, ... in order
                                   of first use) -- what rocprof aggregates per kernel */
@@ -271,8 +272,56 @@ int pifft_plan_create_matrix(pifft_plan** plan, uint64_t n0, uint64_t n1, uint32
 int pifft_plan_dry_run_matrix(uint64_t n0, uint64_t n1, uint32_t batch, int prec, int flags,
                               pifft_plan_info* info);
 
+/* Arbitrary-length 1-D transforms: batch rows of n values, 3 <= n <= 2^27, n NOT
+ * a power of two (a power of two is refused: pifft_plan_create is the faster
+ * answer, and a caller dispatches on n -- plan_1d in pifft.py does),
+ *   X[k] = sum_j x[j] e^{-2 pi i jk/n}, unnormalised; with PIFFT_INVERSE e^{+...}
+ * and no 1/n.  flags: 0 or PIFFT_INVERSE.  Rows lie back to back with row stride
+ * n, in and out; they need only the alignment of their complex type (at fp32 an
+ * odd n puts every other row at 8 mod 16).  d_in != d_out, d_in is never written,
+ * and no byte outside the batch*n values of either buffer is touched.
+ *
+ * A chirp plan is Bluestein's chirp-z algorithm on two power-of-two chains.
+ * With w[j] = e^{-i pi j^2/n} and M the smallest power of two >= 2n - 1:
+ *   a[j] = x[j] w[j] (j < n), 0 (n <= j < M);   Bt = DFT_M(b) / M,
+ *   b[j] = b[M-j] = conj w[j] (j < n), 0 elsewhere;
+ *   X[k] = w[k] IDFT_M(DFT_M(a) Bt)[k],  k < n.
+ * The chains are the two 1-D plans pifft_plan_dry_run describes for (M, 1
+ * worker, natural order, batch), the second with PIFFT_INVERSE, launch for
+ * launch, over two plan-owned staging buffers Z and Y of batch*M values:
+ *   chirp pre (launch_kind 8) d_in -> Z, forward chain Z -> Y, spectrum multiply
+ *   (kind 9) Y in place, inverse chain Y -> Z, chirp post (kind 10) Z -> d_out.
+ * The plan owns Z, Y, one ping-pong workspace (the larger of the two chains'),
+ * both chains' tables, a two-level table of e^{-i pi r/n} (r = j^2 mod 2n, exact
+ * integer arithmetic; about sqrt(2n) entries per level) and Bt (M values):
+ * workspace_bytes.  Bt is fixed at creation, identically for both precisions up
+ * to one final rounding: b is filled on the device in fp64, transformed by a
+ * temporary fp64 plan of (M, 1 worker, batch 1), scaled by the exact 1/M and
+ * rounded once; creation is synchronous.  A PIFFT_INVERSE plan is the forward
+ * plan whose first launch swaps re/im of what it loads from d_in and whose last
+ * launch swaps what it stores to d_out: swap(forward(swap(x))) bit for bit.
+ *
+ * The info of a chirp plan: n = n, local_n = M, workers = num_workers = 1,
+ * tree_launches 0, in_elems = out_elems = batch*n, flags as given, num_passes
+ * and radix / lines / vpt the forward chain's passes then the inverse chain's,
+ * launch_kind / launch_bytes / launch_mode the two inner dry runs' entries with
+ * the new launches (mode 0) around and between them -- kind 8: batch*(n + M)
+ * elements read plus written, 9: batch*2M plus M for Bt once, 10: batch*2n --
+ * layout the OR of the inner plans'.  A plan of more than 8 passes in all is
+ * refused (none at M <= 2^28).  The dry run takes no device.
+ *
+ * A chirp plan runs through the entry points a matrix plan runs through;
+ * pifft_plan_get_dims gives (1, n), pifft_plan_is_real 0; the host-boundary and
+ * multi-plan entry points, tree_device and plan_tune_workspace return -1 on it.
+ * The 1-D, real and matrix entry points keep refusing an n that is no power of
+ * two.  pifft_plan_is_chirp: 0 / 1, -1 for NULL. */
+int pifft_plan_create_chirp(pifft_plan** plan, uint64_t n, uint32_t batch, int prec, int device,
+                            int flags);
+int pifft_plan_dry_run_chirp(uint64_t n, uint32_t batch, int prec, int flags, pifft_plan_info* info);
+int pifft_plan_is_chirp(const pifft_plan* plan);
+
 /* The dimensions a plan was made for: (n0, n1) of a matrix plan; n0 = 1 and
- * n1 = info.n for 1-D and real plans. */
+ * n1 = info.n for 1-D, real and chirp plans. */
 int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1);
 
 /* The grid of launch `launch` (< info.num_launches) in workgroups, for any plan
