@@ -11,6 +11,8 @@
 //   [real plans: the N/2-point chain above plus one fix-up launch (create_real, pifft_real.h)]
 //   [matrix plans: two such chains, rows and columns, with transposes between them (create_matrix, pifft_matrix.h)]
 //   [chirp plans: any length N, two chains of M >= 2N - 1 around a pointwise product (create_chirp, pifft_chirp.h)]
+//   [convolution plans: real rows times one filter, the two chains of a real transform around a fused pair kernel
+//    (create_conv, pifft_conv.h)]
 //
 // Buffers ping-pong between the caller's output and one plan-owned workspace.
 // Twiddles are host-built tables in HBM (w_R per pass, two-level w_M and w_N;
@@ -20,6 +22,7 @@
 #define _GNU_SOURCE  // sincos (reference_omega_levels)
 #endif
 #include "pifft_chirp.h"
+#include "pifft_conv.h"
 #include "pifft_gather.h"
 #include "pifft_kernels.h"
 #include "pifft_matrix.h"
@@ -262,11 +265,15 @@ const void* find_aux_twin(const void* fn, int sw) {
 // plan
 // ---------------------------------------------------------------------------
 enum { STEP_TREE = 1, STEP_PASS = 2, STEP_INTERLEAVE = 3, STEP_TREE_PASS = 4, STEP_R2C_POST = 5, STEP_C2R_PRE = 6,
-       STEP_TRANSPOSE = 7, STEP_CHIRP_PRE = 8, STEP_SPECTRUM_MUL = 9, STEP_CHIRP_POST = 10 };
+       STEP_TRANSPOSE = 7, STEP_CHIRP_PRE = 8, STEP_SPECTRUM_MUL = 9, STEP_CHIRP_POST = 10,
+       STEP_CONV_PAD = 11, STEP_CONV_PAIR = 12, STEP_CONV_CROP = 13,
+       STEP_CONV_FILTER = 14 };  // (14: of pifft_conv_set_filter only, never among a plan's launches)
 // BUF_Z: a real plan's staging buffer, batch x N/2 values (create_real); a
 // matrix plan's, batch x n0 x n1 values (build_matrix); a chirp plan's Z, and
-// BUF_Y its Y, batch x M values each (build_chirp)
-enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, BUF_Y = 5, NBUF = 6 };
+// BUF_Y its Y, batch x M values each (build_chirp); a convolution plan's Z and
+// Y, batch x H values each (a cyclic plan's Z: one row), and BUF_G its filter
+// spectrum G, H + 1 values (build_conv)
+enum { BUF_IN = 0, BUF_OUT = 1, BUF_W = 2, BUF_TA = 3, BUF_Z = 4, BUF_Y = 5, BUF_G = 6, NBUF = 7 };
 
 // a step's twiddle tables as byte offsets into the plan's blob (kNoTable:
 // none); materialise resolves them into pa / ta / ra once, launch_step never
@@ -293,6 +300,7 @@ struct Step {
     RealArgs ra{};  // STEP_R2C_POST / STEP_C2R_PRE
     TransposeArgs xa{};  // STEP_TRANSPOSE
     ChirpArgs ca{};  // STEP_CHIRP_PRE / STEP_SPECTRUM_MUL / STEP_CHIRP_POST
+    ConvArgs va{};   // STEP_CONV_*
     StepTables tab;
     uint64_t bytes = 0;
 };
@@ -322,6 +330,16 @@ struct pifft_plan : pifft::PlanShape {  // (the shape it was planned for, pifft_
     uint64_t chirp_n = 0;
     size_t bytes_y = 0, bytes_bt = 0;
     void* d_bt = nullptr;
+    // pifft_plan_create_conv: batch rows of conv_n reals times one filter of
+    // conv_taps reals, conv_len results per row, over transforms of conv_m
+    // reals.  The shape above is (H = conv_m / 2, one worker, batch); steps,
+    // tables and W are those of the forward and the inverse chain of H
+    // (build_conv).  filter_steps: the launches of pifft_conv_set_filter, with
+    // the forward chain planned for batch 1; conv_ready: G holds a filter
+    bool conv = false, conv_ready = false;
+    uint64_t conv_n = 0, conv_taps = 0, conv_len = 0, conv_m = 0;
+    size_t bytes_g = 0;
+    std::vector<Step> filter_steps;
     std::vector<Step> steps;
     int tree_steps = 0, npasses = 0;
     bool fused_tree = false;  // tree evaluated inside the first pass (STEP_TREE_PASS)
@@ -782,10 +800,15 @@ void add_real_step(pifft_plan* p, TableBuilder& tb, uint64_t n, bool c2r) {
 int materialise(pifft_plan* p, const TableBuilder& tb) {
     HIPCHK(hipMalloc(&p->d_tw, p->tw_bytes + p->rtw_bytes));
     if (p->bytes_bt) HIPCHK(hipMalloc(&p->d_bt, p->bytes_bt));
+    if (p->bytes_g) HIPCHK(hipMalloc(&p->buf[BUF_G], p->bytes_g));
     if (!tb.blob.empty()) HIPCHK(hipMemcpy(p->d_tw, tb.blob.data(), tb.blob.size(), hipMemcpyHostToDevice));
     auto at = [&](size_t off) { return off == kNoTable ? nullptr : (const void*)((const char*)p->d_tw + off); };
     auto resolve = [&](Step& s) {
         if (s.kind == STEP_TRANSPOSE) return;  // (no table, static LDS)
+        if (s.kind >= STEP_CONV_PAD) {
+            s.va.tw_lo = at(s.tab.lo), s.va.tw_hi = at(s.tab.hi), s.va.g = p->buf[BUF_G];
+            return;
+        }
         if (s.kind >= STEP_CHIRP_PRE) {
             s.ca.tw_lo = at(s.tab.lo), s.ca.tw_hi = at(s.tab.hi), s.ca.bt = p->d_bt;
             return;
@@ -798,6 +821,7 @@ int materialise(pifft_plan* p, const TableBuilder& tb) {
     };
     for (Step& s : p->steps) resolve(s);
     for (Step& s : p->tree_only) resolve(s);
+    for (Step& s : p->filter_steps) resolve(s);
     // tuning knob (tools/probe_place.py): hipExtMallocWithFlags flags for the
     // ping-pong workspace, e.g. 4 = hipDeviceMallocContiguous
     const int w_flags = env_int("PIFFT_W_MALLOC_FLAGS", 0);
@@ -1156,6 +1180,146 @@ int create_chirp(pifft_plan** out, uint64_t n, uint32_t batch, int prec, int dev
     return 0;
 }
 
+// Convolution plans (pifft_plan_create_conv; kernels and formulas in
+// pifft_conv.h): batch rows of n reals times one filter of taps reals.  With
+// M = conv_length(n, taps) (cyclic: n) and H = M/2 the plan is the two complex
+// plans plan_chain makes for (H, one worker, natural order, batch) -- untouched;
+// the second with PIFFT_INVERSE, exactly the chains of the real plans of M --
+// around the fused pair kernel, over Z (BUF_Z) and Y (BUF_Y), batch x H values:
+//   linear: [k_conv_pad: d_in -> Z] [forward chain: Z -> Y] [k_conv_pair: Y in place]
+//           [inverse chain: Y -> Z] [k_conv_crop: Z -> d_out]
+//   cyclic: [forward chain: d_in -> Y] [k_conv_pair: Y in place] [inverse chain: Y -> d_out]
+// A chain keeps its own ping-pong (splice, as build_matrix) and W as ever.
+// pifft_conv_set_filter's launches (filter_steps) are planned here too:
+//   [k_conv_filter: d_h -> Z row 0] [forward chain at batch 1: Z -> Y row 0] [k_r2c_post: Y -> G]
+// the chain by plan_chain for (H, one worker, batch 1), whose launches may
+// differ from those for `batch`.  The three chains never run concurrently: one
+// W of the largest size.  All their tables and the two-level table of w_M go
+// into one blob.  A cyclic plan's Z is the one row set_filter needs.
+int build_conv(pifft_plan* p, bool dry) {
+    const uint64_t H = p->n, M = p->conv_m;
+    const bool cyclic = (p->flags & PIFFT_CONV_CYCLIC) != 0;
+    TableBuilder tb(p->esz);
+    tb.size_only = dry;
+    pifft_plan chain[3];  // forward, inverse, forward at batch 1: planned here, never materialised
+    for (int c = 0; c < 3; c++) {
+        pifft_plan& q = chain[c];
+        static_cast<PlanShape&>(q) = plan_shape(H, 1, 0, 1, c == 2 ? 1 : p->batch, p->prec, true, false, false);
+        q.device = -1;
+        q.flags = c == 1 ? PIFFT_INVERSE : 0;
+        q.inverse = c == 1;
+        if (plan_chain(&q, tb)) return -1;
+    }
+    const TwoLevel tw = two_level(tb, M);
+    tb.align();
+    p->tw_bytes = tb.size();
+    if (chain[0].npasses + chain[1].npasses > 8)
+        return fail("convolution plan: %d + %d passes exceed the 8 a plan describes", chain[0].npasses,
+                    chain[1].npasses);
+    p->bytes_z = (size_t)(cyclic ? 1 : p->batch) * H * p->esz;
+    p->bytes_y = (size_t)p->batch * H * p->esz;
+    p->bytes_g = (size_t)(H + 1) * p->esz;
+    p->bytes_w = std::max(std::max(chain[0].bytes_w, chain[1].bytes_w), chain[2].bytes_w);
+    const size_t rsz = p->esz / 2;  // bytes of a real
+    auto stream = [&](std::vector<Step>& to, int step, int kind, uint64_t len, uint32_t batch, int src, int dst,
+                      uint64_t bytes) {
+        Step s;
+        s.kind = step;
+        s.fn = conv_fn(kind, p->prec);
+        const uint64_t units = p->prec == PIFFT_F64 ? conv_units<double>(kind, len, H) : conv_units<float>(kind, len, H);
+        s.block = dim3(256);
+        s.grid = dim3(stride_grid((uint64_t)batch * units));
+        s.va = p->prec == PIFFT_F64 ? conv_args<double>(kind, len, H, batch, (uint64_t)s.grid.x * 256)
+                                    : conv_args<float>(kind, len, H, batch, (uint64_t)s.grid.x * 256);
+        s.va.tw_h = tw.h;
+        s.va.rev = (step == STEP_CONV_FILTER && (p->flags & PIFFT_CONV_CORRELATE)) ? 1u : 0u;
+        s.tab.lo = tw.lo;
+        s.tab.hi = tw.hi;
+        s.src = src;
+        s.dst = dst;
+        s.bytes = bytes;
+        to.push_back(s);
+    };
+    if (!cyclic)
+        stream(p->steps, STEP_CONV_PAD, CONV_PAD, p->conv_n, p->batch, BUF_IN, BUF_Z,
+               (uint64_t)p->batch * (p->conv_n + M) * rsz);
+    splice(p, chain[0], cyclic ? BUF_IN : BUF_Z, BUF_Y);
+    stream(p->steps, STEP_CONV_PAIR, CONV_PAIR, 0, p->batch, BUF_Y, BUF_Y, ((uint64_t)p->batch * 2 * H + H + 1) * p->esz);
+    splice(p, chain[1], BUF_Y, cyclic ? BUF_OUT : BUF_Z);
+    if (!cyclic)
+        stream(p->steps, STEP_CONV_CROP, CONV_CROP, p->conv_len, p->batch, BUF_Z, BUF_OUT,
+               (uint64_t)p->batch * (M + p->conv_len) * rsz);
+    // pifft_conv_set_filter: its d_h stands where an execution's d_in stands
+    stream(p->filter_steps, STEP_CONV_FILTER, CONV_FILTER, p->conv_taps, 1, BUF_IN, BUF_Z, (p->conv_taps + M) * rsz);
+    for (Step s : chain[2].steps) {
+        s.src = s.src == BUF_IN ? BUF_Z : s.src == BUF_OUT ? BUF_Y : s.src;
+        s.dst = s.dst == BUF_OUT ? BUF_Y : s.dst;
+        p->filter_steps.push_back(s);
+    }
+    Step r;
+    r.kind = STEP_R2C_POST;
+    r.fn = aux_fn(PIFFT_AUX_R2C, p->prec);
+    r.tab.lo = tw.lo;
+    r.tab.hi = tw.hi;
+    r.ra.tw_h = tw.h;
+    r.ra.batch = 1;
+    r.ra.h = H;
+    r.ra.units = p->prec == PIFFT_F64 ? real_units<double>(H) : real_units<float>(H);
+    r.block = dim3(256);
+    r.grid = dim3(stride_grid(r.ra.units));
+    r.ra.step_rows = ((uint64_t)r.grid.x * 256) / r.ra.units;
+    r.ra.step_units = ((uint64_t)r.grid.x * 256) % r.ra.units;
+    r.bytes = (2 * H + 1) * p->esz;
+    r.src = BUF_Y;
+    r.dst = BUF_G;
+    p->filter_steps.push_back(r);
+    return dry ? 0 : materialise(p, tb);
+}
+
+int create_conv(pifft_plan** out, uint64_t n, uint64_t taps, uint32_t batch, int prec, int device, int flags,
+                bool dry = false) {
+    if (!out) return fail("plan pointer is NULL");
+    *out = nullptr;
+    if (n == 0 || taps == 0) return fail("Invalid input size (a convolution plan needs n >= 1 and taps >= 1)");
+    if (batch == 0) return fail("batch must be >= 1");
+    if (prec != PIFFT_F32 && prec != PIFFT_F64) return fail("prec must be PIFFT_F32 or PIFFT_F64");
+    if (flags & ~(PIFFT_CONV_CORRELATE | PIFFT_CONV_CYCLIC))
+        return fail("unknown flags %d (a convolution plan takes PIFFT_CONV_CORRELATE and PIFFT_CONV_CYCLIC)", flags);
+    const bool cyclic = (flags & PIFFT_CONV_CYCLIC) != 0;
+    const uint64_t cap = 1ull << 28;
+    if (cyclic) {
+        if (n < 4 || !is_pow2(n)) return fail("Invalid input size (a cyclic convolution plan needs n = 2^i, i > 1)");
+        if (n > cap) return fail("convolution plan too large: a cyclic plan needs n <= 2^28");
+        if (taps > n) return fail("Invalid filter size (a cyclic convolution plan needs taps <= n)");
+    } else if (n > cap || taps > cap || n + taps - 1 > cap) {
+        return fail("convolution plan too large: n + taps - 1 must not exceed 2^28");
+    }
+    if (!dry) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available");
+        if (device < 0 || device >= ndev) return fail("device %d out of range (%d devices)", device, ndev);
+    }
+    const uint64_t M = cyclic ? n : conv_length(n, taps);
+    pifft_plan* p = new pifft_plan;
+    static_cast<PlanShape&>(*p) = plan_shape(M / 2, 1, 0, 1, batch, prec, true, false, false);
+    p->conv = true;
+    p->conv_n = n;
+    p->conv_taps = taps;
+    p->conv_len = cyclic ? n : n + taps - 1;
+    p->conv_m = M;
+    p->device = dry ? -1 : device;
+    p->flags = flags;
+    DeviceGuard g(p->device);
+    if (build_conv(p, dry)) {
+        std::string keep = g_err;
+        release(p);
+        g_err = keep;
+        return -1;
+    }
+    *out = p;
+    return 0;
+}
+
 const char* kRealOnly = "real plans (pifft_plan_create_real) run through pifft_execute_device, "
                         "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
 const char* kMatrixOnly = "matrix plans (pifft_plan_create_matrix) run through pifft_execute_device, "
@@ -1163,8 +1327,10 @@ const char* kMatrixOnly = "matrix plans (pifft_plan_create_matrix) run through p
 const char* kChirpOnly = "chirp plans (pifft_plan_create_chirp) run through pifft_execute_device, "
                          "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
 // why a host-boundary / multi-plan / tree / tuning entry point refuses plan p, or NULL
+const char* kConvOnly = "convolution plans (pifft_plan_create_conv) run through pifft_execute_device, "
+                        "pifft_execute_device_timed, pifft_profile_* and pifft_launch_loop only";
 const char* device_only(const pifft_plan* p) {
-    return p->real ? kRealOnly : p->matrix ? kMatrixOnly : p->chirp_n ? kChirpOnly : nullptr;
+    return p->real ? kRealOnly : p->matrix ? kMatrixOnly : p->chirp_n ? kChirpOnly : p->conv ? kConvOnly : nullptr;
 }
 
 // One launch.  With events (e0, e1): hipExtLaunchKernel binds them to the
@@ -1175,7 +1341,8 @@ const char* device_only(const pifft_plan* p) {
 // (round-2 verdict); kernel-bound events add nothing to the stream.
 int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hipStream_t st,
                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    void* base[NBUF] = {const_cast<void*>(d_in), d_out, p->buf[BUF_W], p->buf[BUF_TA], p->buf[BUF_Z], p->buf[BUF_Y]};
+    void* base[NBUF] = {const_cast<void*>(d_in), d_out,         p->buf[BUF_W], p->buf[BUF_TA],
+                        p->buf[BUF_Z],           p->buf[BUF_Y], p->buf[BUF_G]};
     const char* src = (const char*)base[s.src] + s.src_off * p->esz;
     char* dst = (char*)base[s.dst] + s.dst_off * p->esz;
     auto go = [&](void** args, size_t lds) {
@@ -1234,6 +1401,17 @@ int launch_step(pifft_plan* p, const Step& s, const void* d_in, void* d_out, hip
         case STEP_SPECTRUM_MUL:
         case STEP_CHIRP_POST: {
             ChirpArgs a = s.ca;
+            a.in = src;
+            a.out = dst;
+            void* args[] = {&a};
+            e = go(args, 0);
+            break;
+        }
+        case STEP_CONV_PAD:
+        case STEP_CONV_PAIR:
+        case STEP_CONV_CROP:
+        case STEP_CONV_FILTER: {
+            ConvArgs a = s.va;
             a.in = src;
             a.out = dst;
             void* args[] = {&a};
@@ -1316,6 +1494,8 @@ int check_buffers(const pifft_plan* p, const void* d_in, void* d_out) {
     // k_transpose moves fp32 values in 16-B pairs (pifft_matrix.h): hipMalloc's alignment is enough
     if (p->matrix && (((uintptr_t)d_in | (uintptr_t)d_out) & 15))
         return fail("matrix plans need 16-byte aligned device buffers");
+    if (p->conv && !p->conv_ready)
+        return fail("convolution plan: no filter set (call pifft_conv_set_filter before executing)");
     return 0;
 }
 
@@ -1664,10 +1844,48 @@ int pifft_plan_dry_run_chirp(uint64_t n, uint32_t batch, int prec, int flags, pi
 
 int pifft_plan_is_chirp(const pifft_plan* plan) { return plan ? (plan->chirp_n ? 1 : 0) : -1; }
 
+int pifft_plan_create_conv(pifft_plan** plan, uint64_t n, uint64_t taps, uint32_t batch, int prec, int device,
+                           int flags) {
+    return create_conv(plan, n, taps, batch, prec, device, flags);
+}
+
+int pifft_plan_dry_run_conv(uint64_t n, uint64_t taps, uint32_t batch, int prec, int flags, pifft_plan_info* info) {
+    if (!info) return fail("info is NULL");
+    pifft_plan* p = nullptr;
+    if (create_conv(&p, n, taps, batch, prec, -1, flags, true)) return -1;
+    const int rc = pifft_plan_get_info(p, info);
+    release(p);
+    return rc;
+}
+
+int pifft_conv_set_filter(pifft_plan* p, const void* d_h, void* stream) {
+    if (!p) return fail("plan is NULL");
+    if (!p->conv) return fail("pifft_conv_set_filter: not a convolution plan");
+    if (!d_h) return fail("NULL device buffer");
+    DeviceGuard g(p->device);
+    for (const Step& s : p->filter_steps)
+        if (launch_step(p, s, d_h, nullptr, (hipStream_t)stream)) return -1;
+    p->conv_ready = true;
+    return 0;
+}
+
+int pifft_plan_is_conv(const pifft_plan* plan) { return plan ? (plan->conv ? 1 : 0) : -1; }
+
+int pifft_plan_conv_shape(const pifft_plan* plan, uint64_t* n, uint64_t* taps, uint64_t* out_len, uint64_t* m) {
+    if (!plan || !n || !taps || !out_len || !m) return fail("NULL argument");
+    if (!plan->conv) return fail("pifft_plan_conv_shape: not a convolution plan");
+    *n = plan->conv_n;
+    *taps = plan->conv_taps;
+    *out_len = plan->conv_len;
+    *m = plan->conv_m;
+    return 0;
+}
+
 int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1) {
     if (!plan || !n0 || !n1) return fail("NULL argument");
     *n0 = plan->matrix ? plan->n0 : 1;
-    *n1 = plan->matrix ? plan->n1 : plan->real ? plan->real_n : plan->chirp_n ? plan->chirp_n : plan->n;
+    *n1 = plan->matrix ? plan->n1 : plan->real ? plan->real_n : plan->chirp_n ? plan->chirp_n
+          : plan->conv ? plan->conv_n : plan->n;
     return 0;
 }
 
@@ -1781,6 +1999,12 @@ int pifft_plan_get_info(const pifft_plan* p, pifft_plan_info* info) {
         info->n = p->chirp_n;
         info->in_elems = info->out_elems = (uint64_t)p->batch * p->chirp_n;
         info->workspace_bytes += p->bytes_z + p->bytes_y + p->bytes_bt;
+    }
+    if (p->conv) {  // n = the signal length, in reals as in_elems / out_elems; local_n = H (the shape's); Z, Y and G
+        info->n = p->conv_n;
+        info->in_elems = (uint64_t)p->batch * p->conv_n;
+        info->out_elems = (uint64_t)p->batch * p->conv_len;
+        info->workspace_bytes += p->bytes_z + p->bytes_y + p->bytes_g;
     }
     info->layout = (p->wil ? 1 : 0) | (p->ilv ? 2 : 0);
     info->num_launches = (int)p->steps.size();

@@ -25,8 +25,9 @@ SEPARATE_TREE = 4  # flag bit: the tree never fused into the first pass (CLI -u)
 INVERSE = 8  # flag bit: the unnormalised inverse transform, e^{+2 pi i nk/N} (CLI -i)
 REAL_FORWARD, REAL_INVERSE = 0, 1  # pifft_plan_create_real directions: R2C, C2R
 MATRIX_TRANSPOSED_OUT = 16  # flag bit of pifft_plan_create_matrix: the result left as batch arrays of n1 x n0
+CONV_CORRELATE, CONV_CYCLIC = 32, 64  # flag bits of pifft_plan_create_conv
 KIND_NAMES = {1: "tree", 2: "pass", 3: "interleave", 4: "tree+pass", 5: "r2c", 6: "c2r", 7: "transpose",
-              8: "chirp_pre", 9: "spectrum_mul", 10: "chirp_post"}
+              8: "chirp_pre", 9: "spectrum_mul", 10: "chirp_post", 11: "conv_pad", 12: "conv_pair", 13: "conv_crop"}
 MAX_LAUNCH_INFO = 256  # PIFFT_MAX_LAUNCH_INFO (include/pifft.h)
 
 
@@ -93,6 +94,13 @@ _SIGS = {
     "pifft_plan_dry_run_chirp": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                                 ctypes.POINTER(PlanInfo)]),
     "pifft_plan_is_chirp": (ctypes.c_int, [_P]),
+    "pifft_plan_create_conv": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pifft_plan_dry_run_conv": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                               ctypes.c_int, ctypes.POINTER(PlanInfo)]),
+    "pifft_conv_set_filter": (ctypes.c_int, [_P, _P, _P]),
+    "pifft_plan_is_conv": (ctypes.c_int, [_P]),
+    "pifft_plan_conv_shape": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
     "pifft_plan_get_dims": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "pifft_plan_launch_grid": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
     "pifft_plan_kernel_name": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
@@ -238,8 +246,12 @@ class Plan:
         """pifft_plan_is_chirp: 1 a chirp plan, else 0."""
         return lib().pifft_plan_is_chirp(self._h)
 
+    def is_conv(self) -> int:
+        """pifft_plan_is_conv: 1 a convolution plan, else 0."""
+        return lib().pifft_plan_is_conv(self._h)
+
     def dims(self) -> tuple[int, int]:
-        """pifft_plan_get_dims: (n0, n1) of a matrix plan, (1, n) of a 1-D, real or chirp plan."""
+        """pifft_plan_get_dims: (n0, n1) of a matrix plan, (1, n) of a 1-D, real, chirp or convolution plan."""
         n0, n1 = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().pifft_plan_get_dims(self._h, ctypes.byref(n0), ctypes.byref(n1)), "pifft_plan_get_dims")
         return n0.value, n1.value
@@ -418,6 +430,50 @@ def plan_1d(n: int, batch: int = 1, prec: int = F64, *, inverse: bool = False, d
     return ChirpPlan(n, batch, prec, inverse=inverse, device=device)
 
 
+def _conv_args(n, taps, batch, prec) -> None:
+    """The binding's own checks: what ctypes would wrap silently into the C types."""
+    for name, v, bits in (("n", n, 64), ("taps", taps, 64), ("batch", batch, 32)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0 or v >> bits:
+            raise PifftError(f"{name} = {v!r} is not an unsigned {bits}-bit integer")
+    if prec not in (F32, F64):
+        raise PifftError("prec must be F32 or F64")
+
+
+def _conv_flags(correlate: bool, cyclic: bool) -> int:
+    return (CONV_CORRELATE if correlate else 0) | (CONV_CYCLIC if cyclic else 0)
+
+
+def conv_length(n: int, taps: int) -> int:
+    """M of a linear convolution plan: the smallest power of two >= max(n + taps - 1, 4)."""
+    return max(4, 1 << (n + taps - 2).bit_length())
+
+
+class ConvPlan(Plan):
+    """Batch rows of n reals, each convolved with one real filter of taps values
+    (pifft_plan_create_conv): rows of n + taps - 1 reals, numpy.convolve(x, h);
+    correlate=True: numpy.correlate(x, h, "full"); cyclic=True: n a power of
+    two, rows of n reals, the cyclic convolution.  set_filter before executing.
+    Runs through the device-boundary methods (execute_device,
+    execute_device_timed, profile_*, launch_loop), the others raise PifftError."""
+
+    def __init__(self, n: int, taps: int, batch: int = 1, prec: int = F64, *, correlate: bool = False,
+                 cyclic: bool = False, device: int | None = None):
+        _conv_args(n, taps, batch, prec)
+        h = _P()
+        _check(lib().pifft_plan_create_conv(ctypes.byref(h), n, taps, batch, prec, 0 if device is None else device,
+                                            _conv_flags(correlate, cyclic)), "pifft_plan_create_conv")
+        self._h = h
+        self.info = self._info()
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _check(lib().pifft_plan_conv_shape(self._h, *[ctypes.byref(x) for x in v]), "pifft_plan_conv_shape")
+        self.n, self.taps, self.out_len, self.m = (x.value for x in v)
+
+    def set_filter(self, d_h: int, stream=None) -> None:
+        """pifft_conv_set_filter: the taps reals at device address d_h become the
+        plan's filter (asynchronous on `stream`; not while an execution runs)."""
+        _check(lib().pifft_conv_set_filter(self._h, d_h, _stream(stream)), "pifft_conv_set_filter")
+
+
 def _real_kind(i: PlanInfo) -> int:
     kinds = i.launch_kind[: min(i.num_launches, MAX_LAUNCH_INFO)]
     return 1 if 5 in kinds else 2 if 6 in kinds else 0
@@ -440,6 +496,7 @@ def describe_info(i: PlanInfo) -> dict:
         "inverse": bool(i.flags & INVERSE),
         "real": _real_kind(i),  # 0 complex, 1 R2C, 2 C2R (pifft_plan_is_real)
         "chirp": 8 in i.launch_kind[: min(nl, MAX_LAUNCH_INFO)],  # a chirp plan (pifft_plan_is_chirp)
+        "conv": 12 in i.launch_kind[: min(nl, MAX_LAUNCH_INFO)],  # a convolution plan (pifft_plan_is_conv)
     }
 
 
@@ -584,6 +641,16 @@ def dry_run_chirp(n: int, batch: int = 1, prec: int = F64, *, inverse: bool = Fa
     info = PlanInfo()
     _check(lib().pifft_plan_dry_run_chirp(n, batch, prec, INVERSE if inverse else 0, ctypes.byref(info)),
            "pifft_plan_dry_run_chirp")
+    return describe_info(info)
+
+
+def dry_run_conv(n: int, taps: int, batch: int = 1, prec: int = F64, *, correlate: bool = False,
+                 cyclic: bool = False) -> dict:
+    """The convolution plan that would be built (pifft_plan_dry_run_conv), without a device."""
+    _conv_args(n, taps, batch, prec)
+    info = PlanInfo()
+    _check(lib().pifft_plan_dry_run_conv(n, taps, batch, prec, _conv_flags(correlate, cyclic), ctypes.byref(info)),
+           "pifft_plan_dry_run_conv")
     return describe_info(info)
 
 

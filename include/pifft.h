@@ -123,7 +123,9 @@ typedef struct pifft_plan_info {
     int32_t launch_kind[PIFFT_MAX_LAUNCH_INFO]; /* 1 tree, 2 pass, 3 interleave, 4 tree fused
                                   into a pass, 5 / 6 the R2C / C2R fix-up of a real plan,
                                   7 a transpose of a matrix plan, 8 / 9 / 10 the chirp pre,
-                                  spectrum multiply and chirp post of a chirp plan */
+                                  spectrum multiply and chirp post of a chirp plan,
+                                  11 / 12 / 13 the pad, fused pair and crop of a
+                                  convolution plan */
     int32_t launch_fn[PIFFT_MAX_LAUNCH_INFO]; /* kernel of each launch: launches with the same id
                                   run the same kernel function (ids 0, 1, ... in order
                                   of first use) -- what rocprof aggregates per kernel */
@@ -320,8 +322,84 @@ int pifft_plan_create_chirp(pifft_plan** plan, uint64_t n, uint32_t batch, int p
 int pifft_plan_dry_run_chirp(uint64_t n, uint32_t batch, int prec, int flags, pifft_plan_info* info);
 int pifft_plan_is_chirp(const pifft_plan* plan);
 
+/* Real FFT convolution: batch rows of n >= 1 reals (T = float or double), back
+ * to back with row stride n, each convolved with one real filter of taps >= 1
+ * values shared by all rows.
+ *
+ *   flags 0 (linear): d_out receives batch rows of L = n + taps - 1 reals, row
+ *     stride L: y[j] = sum_i x[j-i] h[i], numpy.convolve(x, h).  M is the
+ *     smallest power of two >= max(L, 4); M <= 2^28.  Input rows, output rows
+ *     and the filter need only the alignment of T; no byte outside the batch*n
+ *     and batch*L values is touched.
+ *   PIFFT_CONV_CYCLIC: n a power of two >= 4, taps <= n, M = n; d_out receives
+ *     n reals per row, y[j] = sum_i x[(j-i) mod n] h[i].  Rows need 16-byte
+ *     alignment, as a real plan's.
+ *   PIFFT_CONV_CORRELATE (with either): numpy.correlate(x, h, "full"), the same
+ *     plan with the filter read back to front.  The flag acts only inside
+ *     pifft_conv_set_filter; every executed launch is the same.
+ * d_in != d_out, and d_in is never written.
+ *
+ * With H = M/2 the plan is the two 1-D plans pifft_plan_dry_run describes for
+ * (H, 1 worker, natural order, batch), the second with PIFFT_INVERSE -- the
+ * chains of the real plans of M reals, launch for launch -- over two plan-owned
+ * staging buffers Z and Y of batch*H complex values:
+ *   linear: pad (launch_kind 11) d_in -> Z: a row's n reals, then zeros up to M
+ *           (rewritten on every execution); forward chain Z -> Y; fused pair
+ *           (kind 12) Y in place; inverse chain Y -> Z; crop (kind 13) Z -> d_out,
+ *           the first L reals of every row.
+ *   cyclic: forward chain d_in -> Y, fused pair, inverse chain Y -> d_out (Z is
+ *           the one row pifft_conv_set_filter needs).
+ * The fused pair kernel does, per pair of bins (k, H-k), what the R2C fix-up
+ * (kind 5), a pointwise complex product with the filter's spectrum G and the
+ * C2R fix-up (kind 6) do in three launches, in registers and with their
+ * operation order: its result equals theirs bit for bit.
+ *
+ * G, H + 1 complex values, belongs to the plan.  pifft_conv_set_filter(plan,
+ * d_h, stream) reads the taps reals at d_h (device memory) and fixes G: the
+ * filter padded with zeros into row 0 of Z -- back to front for a correlation --
+ * and scaled by 1/M (a power of two: exact but for underflow), the forward chain
+ * planned for batch 1 (its launches may differ from the batch's) into Y, the R2C
+ * fix-up into G.  R2C then C2R returns M times its input, so this one 1/M leaves
+ * the executions' result the convolution itself: no factor is left to the
+ * caller.  All in the plan's precision; asynchronous on `stream`; it uses the
+ * plan's workspace and must not overlap an execution.  Calling it again replaces
+ * the filter.  Executing a plan whose filter was never set returns -1.
+ *
+ * The plan owns Z, Y, G, one ping-pong workspace (the largest of the three
+ * chains'), the three chains' tables and the two-level table of e^{-2 pi i k/M}:
+ * workspace_bytes.
+ *
+ * The info of a convolution plan: n = the signal length, local_n = H, workers =
+ * num_workers = 1, tree_launches 0, flags as given; in_elems and out_elems are
+ * counted in REAL values of the precision, not complex ones, because n and L may
+ * be odd: batch*n and batch*L (cyclic: batch*n).  num_passes and radix / lines /
+ * vpt are the forward chain's passes then the inverse chain's, launch_kind /
+ * launch_bytes / launch_mode the two inner dry runs' entries with the new
+ * launches (mode 0) around and between them -- bytes read plus written of kind
+ * 11: batch*(n + M) reals, 12: batch*2H complex values plus H + 1 for G once,
+ * 13: batch*(M + L) reals -- layout the OR of the inner plans'.  A plan of more
+ * than 8 passes in all is refused.  The dry run takes no device.
+ *
+ * A convolution plan runs through the entry points a chirp plan runs through;
+ * pifft_plan_get_dims gives (1, n), pifft_plan_is_real and pifft_plan_is_chirp 0;
+ * the host-boundary and multi-plan entry points, tree_device and
+ * plan_tune_workspace return -1 on it.  The 1-D, real, matrix and chirp entry
+ * points keep refusing flags 32 and 64; these refuse PIFFT_INVERSE, flag 16 and
+ * unknown bits.  pifft_plan_is_conv: 0 / 1, -1 for NULL.  pifft_plan_conv_shape:
+ * n, taps, the output row length (L; cyclic: n) and M. */
+#define PIFFT_CONV_CORRELATE 32
+#define PIFFT_CONV_CYCLIC 64
+int pifft_plan_create_conv(pifft_plan** plan, uint64_t n, uint64_t taps, uint32_t batch, int prec,
+                           int device, int flags);
+int pifft_plan_dry_run_conv(uint64_t n, uint64_t taps, uint32_t batch, int prec, int flags,
+                            pifft_plan_info* info);
+int pifft_conv_set_filter(pifft_plan* plan, const void* d_h, void* stream);
+int pifft_plan_is_conv(const pifft_plan* plan);
+int pifft_plan_conv_shape(const pifft_plan* plan, uint64_t* n, uint64_t* taps, uint64_t* out_len,
+                          uint64_t* m);
+
 /* The dimensions a plan was made for: (n0, n1) of a matrix plan; n0 = 1 and
- * n1 = info.n for 1-D, real and chirp plans. */
+ * n1 = info.n for 1-D, real, chirp and convolution plans. */
 int pifft_plan_get_dims(const pifft_plan* plan, uint64_t* n0, uint64_t* n1);
 
 /* The grid of launch `launch` (< info.num_launches) in workgroups, for any plan
